@@ -8,6 +8,12 @@ HBM (BASELINE.json configs[1]: batch 64 x 2 s white noise, 4->16 kHz, nfft 512, 
 weights, seed 2036).  Clips are independent units: with N ranks every rank processes its own 64
 clips (weak scaling, no data-path collective; clip i -> rank i mod N as reference distrib.py:100);
 timing is barrier + synchronize on both sides, max over ranks.  One JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else the line can carry: the same
+K steps one at a time, the per-launch HIP-event pass (roofline, per-kernel figures), the other BASELINE configurations and the CPU
+baseline (each of them can still be switched off with its --no-* option).  --dump-outputs DIR writes the waveform of the last timed
+step (rank 0's clips, at most 64 MB of them) to DIR/waveform.npy as float32; inputs and weights are seeded, so two builds can be
+compared output for output.
 """
 import argparse
 import json
@@ -266,7 +272,12 @@ def main():
     ap.add_argument('--no-kernel-events', action='store_true', help='skip the per-launch HIP-event pass')
     ap.add_argument('--no-serial-reference', action='store_true', help='skip the one-forward-at-a-time reference loop (ms_per_step_one_at_a_time)')
     ap.add_argument('--no-extra-configs', action='store_true', help='skip the BASELINE config 4 / config 5 lines under extra_configs')
+    ap.add_argument('--full', action='store_true', help='also the secondary measurements: one-at-a-time reference loop, per-launch '
+                                                         'HIP-event pass, BASELINE config 4 / config 5 lines, CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the last timed step\'s waveform (rank 0) to DIR/waveform.npy, float32')
     args = ap.parse_args()
+    if not args.full:                                         # a plain run: the headline figure only
+        args.no_serial_reference = args.no_kernel_events = args.no_extra_configs = args.no_cpu_baseline = True
     if args.cpu_baseline_worker:
         print(json.dumps(cpu_baseline_worker(2.0, FULL_CFG['lr_sr'])))
         return
@@ -346,6 +357,11 @@ def main():
         distrib.barrier()
         dt = time.perf_counter() - t0
         y = pipe.result(ticket)
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        keep = max(1, min(B, 64_000_000 // (4 * y[0].numel())))  # the first clips, at most 64 MB (B = 64: all of them, 8.2 MB)
+        np.save(os.path.join(args.dump_outputs, 'waveform.npy'), y[:keep].float().cpu().numpy())
     dt = distrib.max_over_ranks(dt, dev)
     if dt_serial == dt_serial:
         dt_serial = distrib.max_over_ranks(dt_serial, dev)
