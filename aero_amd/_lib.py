@@ -226,6 +226,12 @@ _PROTOS = {
     'aero_gconv1d_bwd': (i32, [C.POINTER(GconvBwdDesc), vp]),
     'aero_loss_grad': (i32, [vp, vp, i64, C.c_float, C.c_float, i32, vp, fp, vp]),
     'aero_avgpool1d_bwd': (i32, [vp, vp, i32, i32, vp]),
+    'aero_mpd_fold': (i32, [fp, i32, i32, i32, vp, vp]),
+    'aero_mpd_unfold_add': (i32, [fp, i32, i32, i32, fp, vp]),
+    'aero_mpd_conv0_fwd': (i32, [vp, fp, fp, vp, i32, i32, i32, i32, C.c_float, vp]),
+    'aero_mpd_conv0_slabs': (i32, [i32, i32]),
+    'aero_mpd_conv0_bwd': (i32, [vp, vp, fp, fp, fp, fp, i32, fp, fp, i32, i32, i32, i32, vp]),
+    'aero_mpd_act': (i32, [vp, i32, i32, i32, i32, C.c_float, vp]),
 }
 
 EXPORTS = tuple(_PROTOS)

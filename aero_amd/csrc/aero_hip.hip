@@ -3,7 +3,7 @@
 // translation unit against a CPU emulation of the HIP subset, as a test double -- never loaded by
 // the product.)
 //
-// Built by __graft_entry__.build():  hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c -DAERO_PART=k  for k = 0..7 (no 5), IN PARALLEL,
+// Built by __graft_entry__.build():  hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c -DAERO_PART=k  for k = 0..8 (no 5), IN PARALLEL,
 // then one link into aero_amd/libaero_hip.so.  The library is ONE source file cut into six independently compiled parts (each
 // kernel header belongs to exactly one part; a part holds the entry points over its kernels): as a single translation unit it took
 // four minutes to compile; now a change to one header rebuilds one part.  Without -DAERO_PART (the emulator's build) the file is the
@@ -43,6 +43,9 @@
 #if AERO_IN(4)
 #include "k_bwd.h"
 #include "k_disc.h"
+#endif
+#if AERO_IN(8)
+#include "k_mpd.h"
 #endif
 
 #include <stdio.h>
@@ -767,3 +770,46 @@ int aero_stream_destroy(void* stream) {
 #endif  // part 0 (cont.)
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------
+// part 8 -- the edge pieces of the multi-period critic `mpd` (k_mpd.h; discriminators.py:89-147)
+#if AERO_IN(8)
+
+int aero_mpd_fold(const float* x, int32_t B, int32_t L, int32_t p, void* y, void* stream) {
+    const char* err = "";
+    int rc = aero_mpd_fold_launch(x, B, L, p, y, (hipStream_t)stream, &err);
+    return aero_finish(rc, err);
+}
+
+int aero_mpd_unfold_add(const float* g, int32_t B, int32_t L, int32_t p, float* dx, void* stream) {
+    const char* err = "";
+    int rc = aero_mpd_unfold_add_launch(g, B, L, p, dx, (hipStream_t)stream, &err);
+    return aero_finish(rc, err);
+}
+
+int aero_mpd_conv0_fwd(const void* x, const float* w, const float* bias, void* y, int32_t N, int32_t H, int32_t C, int32_t pitch, float slope,
+                       void* stream) {
+    const char* err = "";
+    int rc = aero_mpd_conv0_fwd_launch(x, w, bias, y, N, H, C, pitch, slope, (hipStream_t)stream, &err);
+    return aero_finish(rc, err);
+}
+
+int aero_mpd_conv0_slabs(int32_t N, int32_t H) {
+    if (N < 1 || H < 1) return 0;
+    return (int)aero_mpd_conv0_chunks(N, H, nullptr);
+}
+
+int aero_mpd_conv0_bwd(const void* dyp, const void* x, const float* w, const float* inv_scale, float* dx, float* slabs, int32_t nslab, float* dw,
+                       float* db, int32_t N, int32_t H, int32_t C, int32_t pitch, void* stream) {
+    const char* err = "";
+    int rc = aero_mpd_conv0_bwd_launch(dyp, x, w, inv_scale, dx, slabs, nslab, dw, db, N, H, C, pitch, (hipStream_t)stream, &err);
+    return aero_finish(rc, err);
+}
+
+int aero_mpd_act(void* y, int32_t N, int32_t H, int32_t pitch, int32_t C, float slope, void* stream) {
+    const char* err = "";
+    int rc = aero_mpd_act_launch(y, N, H, pitch, C, slope, (hipStream_t)stream, &err);
+    return aero_finish(rc, err);
+}
+
+#endif  // part 8

@@ -177,12 +177,14 @@ static int aero_avgpool1d_launch(const void* x, void* y, int B, int T, hipStream
 
 // out[0] += sum relu(1 + sign * x[i])      (hinge terms of solver.py:489-496,508-509; sign = +1 / -1)
 // out[0] += sum |a[i] - b[i]|               (feature matching, solver.py:505; b may alias nothing)
+// out[0] += sum (a[i] - sign)^2              (least squares, HiFi-GAN critic discriminators.py:222-243: sign is the target 1 / 0)
 __global__ __launch_bounds__(256) void aero_loss_sum_kernel(const h16* a, const h16* b, int64_t n, float sign, int mode, double* part) {
     __shared__ double red[4];
     double s = 0.0;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         if (mode == 0) s += (double)fmaxf(0.f, 1.f + sign * (float)a[i]);
-        else s += (double)fabsf((float)a[i] - (float)b[i]);
+        else if (mode == 1) s += (double)fabsf((float)a[i] - (float)b[i]);
+        else { const float d = (float)a[i] - sign; s += (double)(d * d); }
     }
     s = aero_wave_sum(s);
     if (aero_lane() == 0) red[aero_wave()] = s;
@@ -200,7 +202,7 @@ __global__ void aero_loss_sum_finish_kernel(const double* part, int nblk, double
 
 static int aero_loss_sum_launch(const void* a, const void* b, int64_t n, float sign, int mode, double* part, int npart, double* out, double weight,
                                 hipStream_t stream, const char** err) {
-    if (!a || (mode == 1 && !b) || !part || !out || n < 1 || npart < 1 || mode < 0 || mode > 1) { *err = "loss_sum: bad arguments"; return AERO_ERR_ARG; }
+    if (!a || (mode == 1 && !b) || !part || !out || n < 1 || npart < 1 || mode < 0 || mode > 2) { *err = "loss_sum: bad arguments"; return AERO_ERR_ARG; }
     int64_t nb = (n + 255) / 256;
     if (nb > npart) nb = npart;
     AERO_LAUNCH(aero_loss_sum_kernel, dim3((unsigned)nb), dim3(256), stream, (const h16*)a, (const h16*)b, n, sign, mode, part);
@@ -451,20 +453,22 @@ static int aero_gconv1d_bwd_launch(const aero_gconv_bwd_desc* d, hipStream_t str
 //   mode 0 (hinge)  g[i] = coef * sign * [1 + sign * a[i] > 0]                  d/da of coef * relu(1 + sign * a)
 //   mode 1 (L1)     g[i] = coef * sgn(a[i] - b[i])                              d/da of coef * |a - b|
 //   mode 2          g[i] = dy[i] * (y[i] > 0 ? 1 : slope)   (a = dy, b = y, coef = slope): LeakyReLU backward for the dense layer
+//   mode 3 (LSGAN)  g[i] = coef * 2 (a[i] - sign)                                d/da of coef * (a - sign)^2 (sign: the target 1 / 0)
 __global__ __launch_bounds__(256) void aero_loss_grad_kernel(const h16* a, const h16* b, int64_t n, float sign, float coef, int mode, h16* g, const float* gl) {
-    if (gl && mode < 2) coef *= gl[0];                           // the upstream factor of the loss, a device scalar (no host read)
+    if (gl && mode != 2) coef *= gl[0];                           // the upstream factor of the loss, a device scalar (no host read)
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         float v;
         if (mode == 0) v = (1.f + sign * (float)a[i] > 0.f) ? coef * sign : 0.f;
         else if (mode == 1) { const float d = (float)a[i] - (float)b[i]; v = d > 0.f ? coef : (d < 0.f ? -coef : 0.f); }
-        else v = (float)a[i] * ((float)b[i] > 0.f ? 1.f : coef);
+        else if (mode == 2) v = (float)a[i] * ((float)b[i] > 0.f ? 1.f : coef);
+        else v = 2.f * coef * ((float)a[i] - sign);
         g[i] = (h16)v;
     }
 }
 
 static int aero_loss_grad_launch(const void* a, const void* b, int64_t n, float sign, float coef, int mode, void* g, const float* gl, hipStream_t stream,
                                  const char** err) {
-    if (!a || !g || n < 1 || mode < 0 || mode > 2 || (mode >= 1 && !b)) { *err = "loss_grad: bad arguments"; return AERO_ERR_ARG; }
+    if (!a || !g || n < 1 || mode < 0 || mode > 3 || ((mode == 1 || mode == 2) && !b)) { *err = "loss_grad: bad arguments"; return AERO_ERR_ARG; }
     int64_t nb = (n + 255) / 256;
     if (nb > 4096) nb = 4096;
     AERO_LAUNCH(aero_loss_grad_kernel, dim3((unsigned)nb), dim3(256), stream, (const h16*)a, (const h16*)b, n, sign, coef, mode, (h16*)g, gl);

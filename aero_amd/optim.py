@@ -21,8 +21,10 @@ from . import _lib
 
 class FlatAdam:
     def __init__(self, params, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, lib=None, model=None):
-        """model: the `Aero` module these parameters belong to (optional).  The kernel writes the weights behind autograd's back, so
-        version counters do not move: after every step `model.repack()` tells the device engine to re-pack them."""
+        """model: the `Aero` module these parameters belong to (optional), or a list of modules (the chained critics of train.py:91-96).
+        The kernel writes the weights behind autograd's back, so version counters do not move: after every step `repack()` of every
+        model tells its device engine to re-pack them.  (With a list, the backward passes hand their gradients to autograd, which adds
+        them into the .grad views of the flat buffer; a single model may write straight into flat_g instead: `_grad_sink`.)"""
         self.model = model
         self.params = [p for p in params if p.requires_grad]
         if not self.params:
@@ -51,7 +53,7 @@ class FlatAdam:
                 p.grad = self.flat_g[o:o + sz].view_as(p)
         self.step_count = 0
         self.fresh = True                                        # flat_g is all zeros (nothing accumulated since zero_grad)
-        if model is not None:                                    # the HIP backward writes its gradients straight into flat_g
+        if model is not None and not isinstance(model, (list, tuple)):      # the HIP backward writes its gradients straight into flat_g
             import weakref
             for m in (model, getattr(model, 'module', None)):    # (distrib.DataParallel: the wrapper and the generator inside)
                 if isinstance(m, torch.nn.Module):
@@ -111,15 +113,18 @@ class FlatAdam:
             lib.call('aero_adam_step_dev', self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
                      self.n, C.c_float(self.lr), C.c_float(self.betas[0]), C.c_float(self.betas[1]), C.c_float(self.eps), self._bc.data_ptr(),
                      C.c_float(grad_scale), stream)
-            if self.model is not None and hasattr(self.model, 'repack'):
-                self.model.repack()
+            self._repack()
             return
         self.step_count += 1
         lib.call('aero_adam_step', self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
                  self.n, C.c_float(self.lr), C.c_float(self.betas[0]), C.c_float(self.betas[1]), C.c_float(self.eps), self.step_count,
                  C.c_float(grad_scale), stream)
-        if self.model is not None and hasattr(self.model, 'repack'):
-            self.model.repack()
+        self._repack()
+
+    def _repack(self):
+        for m in (self.model if isinstance(self.model, (list, tuple)) else [self.model]):
+            if m is not None and hasattr(m, 'repack'):
+                m.repack()
 
     # ---- HIP-graph replay (aero_amd.train.CapturedStep)
     _bc = None

@@ -1,7 +1,7 @@
 """One training step of BASELINE config 5 as the reference's entry point runs it (`train.py ddp=true`):
 
-    build_models      <- src/models/modelFactory.py:6-29   generator + the `msd_melgan` critic of the experiment file
-    build_optimizers  <- train.py:83-92                    Adam(generator), Adam(critics), lr / betas from the config
+    build_models      <- src/models/modelFactory.py:6-29   generator + the critics (`msd_melgan`, `mpd`) of the experiment file
+    build_optimizers  <- train.py:83-96                    Adam(generator), Adam(chained critics), lr / betas from the config
     TrainStep         <- src/solver.py:51 (every model through distrib.wrap), :296-320 (forward, losses, optimise),
                          :428-470 (which losses), :475-520 (MelGAN hinge / feature matching), :602-611 (the two optimiser steps)
 
@@ -17,33 +17,49 @@ from .optim import FlatAdam
 
 
 def build_models(args):
-    """modelFactory.py:6-29 for what aero's experiment files use: `model: aero` and, with `adversarial: true`, the MelGAN multi-scale
-    critic.  (Seanet and the HiFi-GAN critics appear in no aero config: NotImplementedError, as `src.models.modelFactory`.)"""
+    """modelFactory.py:6-29 for what aero's experiment files use: `model: aero` and, with `adversarial: true`, the critics of
+    `discriminator_models`: the MelGAN multi-scale critic `msd_melgan` and the HiFi-GAN multi-period critic `mpd`, constructed in
+    modelFactory.py's fixed order (msd_melgan, then mpd) whatever the list order, so a seed draws the reference's initial weights.
+    `mpd` takes its kwargs from `experiment.mpd`; without that block the constructor's defaults are used (the reference would fail on the
+    missing key).  Seanet and the critics `msd_hifi` / `hifi` stay NotImplementedError: the reference cannot run them either."""
     from .modules import Aero
     exp = args.experiment
     if exp.model != 'aero':
         raise NotImplementedError(f"model '{exp.model}': only the AERO generator is implemented on MI355X")
     models = {'generator': Aero(**dict(exp.aero))}
     if exp.get('adversarial'):
-        from .discriminators import Discriminator
-        for name in exp.discriminator_models:
-            if name != 'msd_melgan':
-                raise NotImplementedError(f"critic '{name}': only msd_melgan (the critic of every aero experiment file) is implemented")
-            models[name] = Discriminator(**dict(exp.melgan_discriminator))
+        names = list(exp.discriminator_models)
+        for name in names:
+            if name in ('msd_hifi', 'hifi'):
+                raise NotImplementedError(
+                    f"critic '{name}': not built -- the reference cannot run it (modelFactory.py:18-27 registers the module as 'msd' while "
+                    f"solver.py:525,558 / train.py:92-94 look up 'msd_hifi', and 'hifi' needs a melspec_transform only created under an "
+                    f"experiment key no config sets, solver.py:89-94)")
+            if name not in ('msd_melgan', 'mpd'):
+                raise NotImplementedError(f"critic '{name}': only msd_melgan and mpd are implemented")
+        if 'msd_melgan' in names:
+            from .discriminators import Discriminator
+            models['msd_melgan'] = Discriminator(**dict(exp.melgan_discriminator))
+        if 'mpd' in names:
+            from .mpd import MultiPeriodDiscriminator
+            models['mpd'] = MultiPeriodDiscriminator(**dict(exp.get('mpd') or {}))
     return models
 
 
 def build_optimizers(models, args, lib=None):
-    """train.py:83-92: Adam(lr, betas=(0.9, beta2)) for the generator and one Adam over the chained critics' parameters."""
+    """train.py:83-96: Adam(lr, betas=(0.9, beta2)) for the generator and one Adam over the critics' parameters chained in
+    `discriminator_models` order."""
     if args.optim != 'adam':
         raise ValueError('Invalid optimizer %s' % args.optim)
     gen = models['generator']
     opts = {'optimizer': FlatAdam(gen.parameters(), lr=args.lr, betas=(0.9, args.beta2), lib=lib, model=gen)}
-    critics = [m for k, m in models.items() if k != 'generator']
+    order = [n for n in args.experiment.get('discriminator_models', []) if n in models] if args.experiment.get('adversarial') else []
+    order += [k for k in models if k != 'generator' and k not in order]
+    critics = [models[k] for k in order]
     if critics:
-        if len(critics) != 1:
-            raise NotImplementedError('one critic (msd_melgan) per experiment')
-        opts['disc_optimizer'] = FlatAdam(critics[0].parameters(), lr=args.lr, betas=(0.9, args.beta2), lib=lib, model=critics[0])
+        params = [p for m in critics for p in m.parameters()]
+        opts['disc_optimizer'] = FlatAdam(params, lr=args.lr, betas=(0.9, args.beta2), lib=lib,
+                                          model=critics[0] if len(critics) == 1 else critics)
     return opts
 
 
@@ -74,7 +90,7 @@ class TrainStep:
         if self.mrstft is not None:
             sc, mag = self.mrstft(pr.squeeze(1), hr.squeeze(1))
             out['generator']['stft'] = sc + mag
-        if self.adversarial:
+        if self.adversarial and 'msd_melgan' in self.dmodels:
             exp = self.args.experiment
             critic = self.dmodels['msd_melgan']
             md = exp.melgan_discriminator
@@ -88,6 +104,15 @@ class TrainStep:
             # D(fake.detach()), D(real) on the weights the generator's losses just used (solver.py:478-480): the critic keeps that
             # record, so this costs no second forward
             out['discriminator']['msd_melgan'] = critic.discriminator_loss(pr.detach(), hr)
+        if self.adversarial and 'mpd' in self.dmodels:                        # solver.py:457-463,580-600
+            exp = self.args.experiment
+            mpd = self.dmodels['mpd']
+            adv, feat = mpd.generator_losses(pr, hr, features_loss_lambda=exp.features_loss_lambda)
+            if not exp.get('only_features_loss'):
+                out['generator']['adversarial_mpd'] = adv
+            if not exp.get('only_adversarial_loss'):
+                out['generator']['features_mpd'] = feat
+            out['discriminator']['mpd'] = mpd.discriminator_loss(pr.detach(), hr)
         return out
 
     def __call__(self, lr, hr):

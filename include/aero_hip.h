@@ -570,7 +570,8 @@ int aero_leaky_relu(void* x, int64_t n, float slope, void* stream);             
 /* nn.AvgPool1d(4, stride=2, padding=1, count_include_pad=False) (discriminators.py:70): x fp16 [B][T] -> y fp16 [B][(T-2)/2+1] */
 int aero_avgpool1d(const void* x, void* y, int32_t B, int32_t T, void* stream);
 /* reductions of the hinge / feature-matching losses (solver.py:489-512): out[0] += weight * sum relu(1 + sign * a[i]) (mode 0) or
- * weight * sum |a[i] - b[i]| (mode 1) -- the weight carries the 1 / numel of the mean and the loss coefficients, so a whole loss is one scalar; a, b fp16 [n]; part: scratch of npart doubles; block partials added in order (deterministic). */
+ * weight * sum |a[i] - b[i]| (mode 1) or weight * sum (a[i] - sign)^2 (mode 2: the least-squares terms of the HiFi-GAN critic `mpd`,
+ * discriminators.py:222-243 -- sign is the target 1 / 0) -- the weight carries the 1 / numel of the mean and the loss coefficients, so a whole loss is one scalar; a, b fp16 [n]; part: scratch of npart doubles; block partials added in order (deterministic). */
 int aero_loss_sum(const void* a, const void* b, int64_t n, float sign, int32_t mode, double* part, int32_t npart, double* out, double weight,
                   void* stream);
 
@@ -606,10 +607,31 @@ int aero_weightnorm_fwd(const float* v, const float* g, float* w, int32_t Cout, 
 int aero_gconv1d_wgrad_slabs(int32_t B, int32_t Tin, int32_t Cin, int32_t Cout, int32_t groups, int32_t K, int32_t stride, int32_t pad,
                              int32_t reflect);    /* 0: the MFMA form does not take this layer */
 /* gradients of the loss terms as fp16: mode 0 g = coef * sign * [1 + sign a > 0] (hinge, solver.py:489-496,508), mode 1
- * g = coef * sgn(a - b) (L1, solver.py:505), mode 2 g = a * (b > 0 ? 1 : coef) (LeakyReLU backward: a = dy, b = y, coef = slope) */
+ * g = coef * sgn(a - b) (L1, solver.py:505), mode 2 g = a * (b > 0 ? 1 : coef) (LeakyReLU backward: a = dy, b = y, coef = slope),
+ * mode 3 g = 2 coef (a - sign) (least squares, discriminators.py:222-243; b unused) */
 int aero_loss_grad(const void* a, const void* b, int64_t n, float sign, float coef, int32_t mode, void* g, const float* gl, void* stream);
-/* (gl: optional device scalar multiplied into coef for modes 0 / 1 -- the upstream factor of the loss, read on the device) */
+/* (gl: optional device scalar multiplied into coef for modes 0 / 1 / 3 -- the upstream factor of the loss, read on the device) */
 int aero_avgpool1d_bwd(const void* dy, void* dx, int32_t B, int32_t T, void* stream);      /* adjoint of aero_avgpool1d */
+
+/* HiFi-GAN multi-period critic `mpd` (discriminators.py:89-147, csrc/k_mpd.h).  Column j of clip b of the period-p view [B, 1, H, p] is item
+ * n = b p + j of a channels-last row signal [N = B p][rows][C], H = ceil(L / p); a (5, 1) conv with stride (3, 1) reads its input as
+ * [N][rows / 3][3 C], so the producer of such an input stores pitch = 3 ceil(H / 3) rows per item with the rows past H zero.
+ *   aero_mpd_fold        x fp32 [B][L] -> y fp16 [B p][H]: reflect padding on the right to H p samples (discriminators.py:110-115)
+ *   aero_mpd_unfold_add  its adjoint: dx fp32 [B][L] += the column gradient g fp32 [B p][H], the padded tail folded back onto its mirror
+ *   aero_mpd_conv0_fwd   Conv2d(1, C, (5, 1), (3, 1), padding (2, 0)) + bias + LeakyReLU(slope) (discriminators.py:97,117-118): x fp16 [N][H],
+ *                        w fp32 [C][5] (weight norm applied), bias fp32 [C] -> y fp16 [N][pitch][C], rows Ho = ceil(H / 3) .. pitch - 1 zero
+ *   aero_mpd_conv0_bwd   dyp fp16 [N][pitch][C]: gradient of the PRE-activation output.  dx fp32 [N][H] (may be NULL) WRITTEN, times inv_scale[0]
+ *                        (may be NULL = 1); dw fp32 [C][5], db fp32 [C] (may be NULL) WRITTEN as the in-order sum of per-chunk slabs (workspace
+ *                        slabs fp32 [nslab][6 C], nslab >= aero_mpd_conv0_slabs(N, H)): deterministic, no atomics.  C <= 256.
+ *   aero_mpd_act         y fp16 [N][pitch][C] in place: LeakyReLU on rows < H, rows H .. pitch - 1 zeroed (behind aero_conv_fwd) */
+int aero_mpd_fold(const float* x, int32_t B, int32_t L, int32_t p, void* y, void* stream);
+int aero_mpd_unfold_add(const float* g, int32_t B, int32_t L, int32_t p, float* dx, void* stream);
+int aero_mpd_conv0_fwd(const void* x, const float* w, const float* bias, void* y, int32_t N, int32_t H, int32_t C, int32_t pitch, float slope,
+                       void* stream);
+int aero_mpd_conv0_slabs(int32_t N, int32_t H);
+int aero_mpd_conv0_bwd(const void* dyp, const void* x, const float* w, const float* inv_scale, float* dx, float* slabs, int32_t nslab, float* dw,
+                       float* db, int32_t N, int32_t H, int32_t C, int32_t pitch, void* stream);
+int aero_mpd_act(void* y, int32_t N, int32_t H, int32_t pitch, int32_t C, float slope, void* stream);
 
 /* RCCL over xGMI behind the same ABI (replaces the NCCL process group of the reference's src/ddp/distrib.py:16-34 for a
  * host that is not PyTorch).  One communicator per process, one process per GPU (hipSetDevice first).  Rank 0 calls aero_comm_unique_id
