@@ -6,9 +6,9 @@ same RNG stream at construction (so a seed reproduces the reference's initial we
 kernels of csrc/k_disc.h (grouped strided Conv1d with bias + LeakyReLU fused, the dense k = 5 layer on aero_conv_fwd, AvgPool1d
 between the scales) and returns the reference's structure: a list (scales) of lists (7 feature maps, the last one the logits),
 each [B, C, T] like nn.Conv1d's output (fp16 values, channels-last storage viewed in the reference layout).
-The critic's own step (solver.py:607-611) and the generator's adversarial / feature-matching losses are the autograd functions
-`discriminator_loss` / `generator_losses` below, whose backward runs on the same kernel family; wrapped by `distrib.wrap` (solver.py:51
-wraps every model) the parameter gradients are averaged over the ranks inside that backward (`_grad_sync`, one flat all-reduce)."""
+The generator's adversarial / feature-matching losses are the autograd function `generator_losses` below, whose backward runs on the
+same kernel family; the cached D(fake) || D(real) pair, the critic's own step (`discriminator_loss`) and the delivery of its gradients
+are the shared protocol of aero_amd/critic.py."""
 import ctypes as C
 
 import torch
@@ -16,7 +16,8 @@ from torch import nn
 from torch.nn.utils import weight_norm
 
 from . import _lib, pack
-from .engine import Ops, _ptr
+from .critic import HipCritic, _loss_sum, _scaled_grad, _upstream
+from .engine import _ptr
 from .modules import capture_init
 
 
@@ -91,8 +92,9 @@ def gconv_mfma_images(w, groups, dev):
     return cvt(fwd), cvt(dg)
 
 
-class Discriminator(nn.Module):
-    _supports_grad_sync = True                                   # distrib.wrap: the backward of `discriminator_loss` averages the gradients itself
+class Discriminator(HipCritic):
+    # solver.py:489-496: sum over scales of relu(1 + D(fake)).mean() + relu(1 - D(real)).mean(): (sign, mode) of aero_loss_sum / aero_loss_grad
+    _loss_terms = _grad_terms = ((1.0, 0), (-1.0, 0))
 
     @capture_init
     def __init__(self, num_D, ndf, n_layers, downsampling_factor):
@@ -103,50 +105,25 @@ class Discriminator(nn.Module):
             self.model[f'disc_{i}'] = NLayerDiscriminator(ndf, n_layers, downsampling_factor)
         self.downsample = nn.AvgPool1d(4, stride=2, padding=1, count_include_pad=False)
         self.apply(weights_init)
-        self._ops, self._packed, self._key = None, None, None
-        self._pair, self._epoch = None, 0
         self._builders = {}
-
-    def repack(self):
-        """the weights were edited behind autograd's version counters (FlatAdam's fused step): re-pack on the next forward"""
-        self._pair = None
-        self._epoch += 1
-
-    def use_library(self, lib):
-        """tests: an explicitly loaded library (the CPU-emulated test double)"""
-        self._ops = Ops(lib)
-
-    def _get_ops(self):
-        if self._ops is None:
-            self._ops = Ops(_lib.load())
-        return self._ops
 
     def _pack(self, dev):
         """the layers' device images for the current weights.  Weight norm first (w = g v / |v|, one launch per conv into a persistent
         flat fp32 buffer), then every image -- fp16 [Cout][K][cig], the MFMA images of the grouped layers, the dense layer's conv and
         data-gradient images -- is pure data movement of w and the biases: built by their closures once, and from the first weight
         change on replayed by one gather launch per arena (aero_amd/repack.py), as the generator's training engine does."""
-        dev = torch.device(dev)
-        if dev.type == 'cuda' and dev.index is None:
-            dev = torch.device('cuda', torch.cuda.current_device())
-        key = (str(dev),) + tuple((p.data_ptr(), p._version) for p in self.parameters()) + (self._epoch,)
+        dev, key = self._pack_key(dev)
         if key == self._key:
             return self._packed
         first = self._packed is None
         ops = self._get_ops()
         convs = [(si, j, conv, g) for si, disc in enumerate(self.model.values()) for j, (conv, g) in enumerate(zip(disc.convs(), disc.geom))]
         if self._wflat is None or self._wflat.device != dev:
-            offs, n = [], 0
-            for _, _, conv, _ in convs:
-                offs.append(n)
-                n += (conv.weight_v.numel() + 3) // 4 * 4
-            self._wflat, self._woffs = torch.empty(n, dtype=torch.float32, device=dev), offs
-            self._replay, self._builders = None, {}
+            self._wflat, self._replay, self._builders = None, None, {}
+        # the PERSISTENT buffer, rewritten in place: the gather replay below reads the weights at the addresses it was compiled with
+        self._wflat, ws = self._weightnorm_fwd([conv for _, _, conv, _ in convs], dev, self._wflat)
         sd = {}
-        for (si, j, conv, g), o in zip(convs, self._woffs):
-            v, gg = conv.weight_v.detach(), conv.weight_g.detach()
-            w = self._wflat[o:o + v.numel()].view(v.shape)
-            ops.lib.call('aero_weightnorm_fwd', _ptr(v.contiguous()), _ptr(gg.contiguous()), _ptr(w), v.shape[0], v.shape[1] * v.shape[2], ops.stream(w))
+        for (si, j, conv, g), w in zip(convs, ws):
             sd[f'{si}.{j}.w'], sd[f'{si}.{j}.b'] = w, conv.bias.detach()
         self._sd = sd
 
@@ -191,15 +168,12 @@ class Discriminator(nn.Module):
         self._packed, self._key = packed, key
         return packed
 
-    _wflat, _woffs, _replay, _builders, _sd, replay_enabled = None, None, None, {}, None, True
+    _wflat, _replay, _builders, _sd, replay_enabled = None, None, {}, None, True
 
     def _run(self, x):
         """-> per scale: (waveform fp16 [B, T_s], [(layer entry, input h [B,T,Cin], output y [B,T',Cout]) ...])"""
+        self._check_input(x)
         ops = self._get_ops()
-        if not x.is_cuda and not ops.lib.is_emulator:
-            raise RuntimeError('aero_amd.discriminators runs on the MI355X: move the signals to "cuda"')
-        if x.dim() != 3 or x.shape[1] != 1:
-            raise ValueError('expected a [B, 1, T] waveform')
         dev = x.device
         packed = self._pack(dev)
         B = x.shape[0]
@@ -234,21 +208,6 @@ class Discriminator(nn.Module):
                 cur = nxt
         return scales
 
-    def _run_pair(self, fake, real):
-        """D(fake) and D(real) as ONE batch of 2B signals (the reference runs the critic twice per loss, solver.py:478-480,505-506: the
-        same arithmetic per signal, half the launches), kept until the weights or the signals change: the critic's own step
-        (solver.py:607-611) evaluates D on exactly the signals and weights the generator's adversarial / feature losses just used, so
-        its forward pass is this record again.  Returns (record of the 2B batch, B)."""
-        if fake.shape != real.shape:
-            raise ValueError('fake and real must have the same shape')
-        key = (fake.data_ptr(), fake._version, real.data_ptr(), real._version, tuple(fake.shape), str(fake.device)) + \
-            tuple((p.data_ptr(), p._version) for p in self.parameters()) + (self._epoch,)
-        if self._pair is None or self._pair[0] != key:
-            # (the record keeps the two signals alive: while it is cached their memory cannot be recycled for other data at the same
-            # address and version -- a key built from pointers alone would then hit a stale record, e.g. in a validation loop)
-            self._pair = (key, self._run(torch.cat([fake.detach(), real.detach()], 0)), fake.detach(), real.detach())
-        return self._pair[1], fake.shape[0]
-
     @staticmethod
     def _half(runs, lo, hi):
         """the record of batch items [lo, hi) of a run (views)"""
@@ -260,11 +219,9 @@ class Discriminator(nn.Module):
         return [[y.permute(0, 2, 1) for (_, _, y) in recs] for (_, recs) in self._run(x)]
 
     # ------------------------------------------------------------------ losses with their HIP backward (solver.py:475-520)
-    def discriminator_loss(self, fake, real):
-        """solver.py:489-496: sum over scales of relu(1 + D(fake)).mean() + relu(1 - D(real)).mean(); differentiable w.r.t. the
-        critic's parameters (the generator output is detached, solver.py:479)"""
-        names, params = zip(*self.named_parameters())
-        return _CriticLoss.apply(self, names, fake.detach(), real.detach(), *params)
+    def _logit_heads(self, runs, B):
+        """per scale: (logits of the 2B batch fp16 [2B, T', 1], rows of D(fake))"""
+        return [(recs[-1][2], B) for (_, recs) in runs]
 
     def generator_losses(self, fake, real, n_layers=4, features_loss_lambda=100.0):
         """solver.py:498-520: (adversarial = sum relu(1 - D(fake)).mean(), lambda * feature matching); differentiable w.r.t. `fake`"""
@@ -289,11 +246,7 @@ class Discriminator(nn.Module):
             for j in reversed(range(len(recs))):
                 ent, h, y = recs[j]
                 if j < len(recs) - 1:
-                    f = dfeat[si][j] if dfeat is not None else None
-                    if f is not None:
-                        g, sc = TO.rescale_f16(ops, dx, sc, f[0], f[1])
-                    else:
-                        g, sc = TO.rescale_f16(ops, dx, sc)
+                    g, sc = self._join_feature_grad(dx, sc, dfeat, si, j)
                 Tin, To = h.shape[1], y.shape[1]
                 conv = disc.convs()[j]
                 prefix = f'model.disc_{si}.model.{keys[j]}.' + ('1.' if keys[j] == 'layer_0' else ('0.' if isinstance(disc.model[keys[j]], nn.Sequential) else ''))
@@ -331,20 +284,7 @@ class Discriminator(nn.Module):
                         cig_ = ent['Cin'] // ent['groups']
                         dw_strides = (ent['K'] * cig_, 1, cig_)                      # [Cout, K, cig]: element (o, c, k)
                 if want_params:
-                    # weight norm (w = g v / |v| per output channel), the 1 / S of the fp16 gradient path and the upstream loss factor in
-                    # ONE launch (aero_weightnorm_bwd) -- the same bookkeeping in torch ops was ~20 parameter-sized kernels per conv
-                    v, gg = conv.weight_v.detach(), conv.weight_g.detach()
-                    assert v.dtype == torch.float32 and v.is_contiguous() and gg.is_contiguous()
-                    names3 = (prefix + 'weight_g', prefix + 'weight_v', prefix + 'bias')
-                    if out is not None:
-                        dg_, dv_, dbias_ = (out[n] for n in names3)
-                        acc = 1
-                    else:
-                        dg_, dv_, dbias_ = torch.empty_like(gg), torch.empty_like(v), torch.empty(v.shape[0], dtype=torch.float32, device=v.device)
-                        acc = 0
-                        grads[names3[0]], grads[names3[1]], grads[names3[2]] = dg_, dv_, dbias_
-                    ops.lib.call('aero_weightnorm_bwd', _ptr(dwk), dw_strides[0], dw_strides[1], dw_strides[2], _ptr(v), _ptr(gg), _ptr(db),
-                                 sc[1:].data_ptr(), _ptr(gl), _ptr(dg_), _ptr(dv_), _ptr(dbias_), v.shape[0], v.shape[1], v.shape[2], acc, ops.stream(v))
+                    grads.update(self._weightnorm_bwd(conv, prefix, dwk, dw_strides, db, sc, gl, out))
             if want_input:
                 dxw = dx.view(B, -1)                             # gradient of this scale's waveform
                 if dwave is not None:                            # + the coarser scales through the AvgPool1d between them
@@ -363,97 +303,6 @@ class Discriminator(nn.Module):
     def _wn(conv):
         v, gg = conv.weight_v.detach().float(), conv.weight_g.detach().float()
         return v * (gg / v.flatten(1).norm(dim=1).view(-1, 1, 1))
-
-
-def _scaled_grad(ops, a, b, n_mean, sign, coef, mode, out=None, gl=None):
-    """gradient of coef * mean(...) as fp16 with a host-chosen power-of-two scale: returns (tensor, {S, 1/S} on the device)"""
-    import math
-    c = coef / n_mean
-    S = 2.0 ** round(math.log2(32.0 / max(abs(c), 1e-30)))
-    g = torch.empty(a.shape, dtype=torch.float16, device=a.device) if out is None else out
-    assert a.is_contiguous() and g.is_contiguous() and (b is None or b.is_contiguous())
-    ops.lib.call('aero_loss_grad', _ptr(a), _ptr(b), a.numel(), C.c_float(sign), C.c_float(c * S), mode, _ptr(g), _ptr(gl), ops.stream(a))
-    return g, _scale_pair(S, a.device)
-
-
-_SCALES = {}
-
-
-def _scale_pair(S, dev):
-    """{S, 1/S} on the device (cached: host-chosen powers of two, a handful of distinct values)"""
-    key = (S, str(dev))
-    if key not in _SCALES:
-        _SCALES[key] = torch.tensor([S, 1.0 / S], dtype=torch.float32, device=dev)
-    return _SCALES[key]
-
-
-class _CriticLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, disc, names, fake, real, *params):
-        ops = disc._get_ops()
-        runs, B = disc._run_pair(fake, real)
-        loss = torch.zeros(1, dtype=torch.float64, device=fake.device)
-        for (_, recs) in runs:
-            logits = recs[-1][2]
-            w = 1.0 / logits[:B].numel()                         # (the means and the sum over scales accumulate in one device scalar)
-            _loss_sum(ops, logits[:B], None, 1.0, 0, loss, w)
-            _loss_sum(ops, logits[B:], None, -1.0, 0, loss, w)
-        ctx.disc, ctx.names, ctx.runs, ctx.B = disc, names, runs, B
-        ctx.param_ptrs, ctx.shapes = [p.data_ptr() for p in params], [p.shape for p in params]
-        return loss[0].float()
-
-    @staticmethod
-    def backward(ctx, gl):
-        disc, ops = ctx.disc, ctx.disc._get_ops()
-        B = ctx.B
-        # one backward pass over the 2B batch: d relu(1 + D(fake)).mean() on the first half, d relu(1 - D(real)).mean() on the second
-        dtop = []
-        for (_, recs) in ctx.runs:
-            logits = recs[-1][2]
-            g = torch.empty_like(logits)
-            _, sc = _scaled_grad(ops, logits[:B], None, logits[:B].numel(), 1.0, 1.0, 0, out=g[:B])
-            _scaled_grad(ops, logits[B:], None, logits[B:].numel(), -1.0, 1.0, 0, out=g[B:])
-            dtop.append((g, sc))
-        # FlatAdam keeps every parameter's .grad as a view of one flat buffer: write there (freshly zeroed by zero_grad) and hand autograd no
-        # per-parameter gradients (its AccumulateGrad nodes were one `grad += g` launch per parameter) -- as aero_amd.train.AeroFunction does
-        glf = gl.detach().float().contiguous()
-        # distrib.wrap(critic) (solver.py:51): the mean over ranks.  1 / world rides in the upstream factor the weight-norm kernel
-        # multiplies in anyway; the sum is ONE all-reduce over the flat gradient range once the pass is done (the critic's backward is a
-        # few milliseconds: nothing to overlap it with but the optimizer step that needs its result)
-        sync = getattr(disc, '_grad_sync', None)
-        if sync is not None and not sync.active():
-            sync = None
-        if sync is not None:
-            glf = glf * sync.mean_factor()
-        sink = getattr(disc, '_grad_sink', None)
-        sink = sink() if sink is not None else None
-        offs, n = [], 0
-        for shp in ctx.shapes:
-            offs.append(n)
-            n += (shp.numel() + 3) // 4 * 4
-        params = dict(disc.named_parameters())
-        # (a buffer that already holds gradients must not go through the collective a second time: then this pass gets its own tensors)
-        if sink is not None and sink.accepts(ctx.param_ptrs, offs, n, glf.device) and (sync is None or sink.fresh):
-            out = {nme: params[nme].grad for nme in ctx.names}
-            sink.fresh = False
-            disc._backward(ctx.runs, dtop, None, True, False, out=out, gl=glf)
-            ctx.runs = None
-            if sync is not None:
-                sync.reduce_async(sink.flat_g)
-                sync.wait()
-            return (None, None, None, None) + (None,) * len(ctx.names)
-        total, _ = disc._backward(ctx.runs, dtop, None, True, False, gl=glf)
-        ctx.runs = None
-        if sync is not None:
-            flat = torch.cat([total[nme].reshape(-1) for nme in ctx.names])
-            sync.reduce_async(flat)
-            sync.wait()
-            o = 0
-            for nme in ctx.names:
-                k = total[nme].numel()
-                total[nme] = flat[o:o + k].view_as(total[nme])
-                o += k
-        return (None, None, None, None) + tuple(total[n] for n in ctx.names)
 
 
 class _GeneratorLoss(torch.autograd.Function):
@@ -479,24 +328,13 @@ class _GeneratorLoss(torch.autograd.Function):
         disc, ops = ctx.disc, ctx.disc._get_ops()
         rf, rr = ctx.runs
         w_feat, lam = ctx.cfg
-        # the upstream factors (1 in solver.py:314-316) stay on the device: the loss-gradient kernel multiplies them in (a float() here
-        # would stall the host in the middle of the generator's backward until the device had caught up)
-        ga, gf = gadv.detach().float().contiguous(), gfeat.detach().float().contiguous()
+        ga, gf = _upstream(gadv), _upstream(gfeat)
         dtop = [_scaled_grad(ops, recs[-1][2], None, recs[-1][2].numel(), -1.0, 1.0, 0, gl=ga) for (_, recs) in rf]
         dfeat = [[_scaled_grad(ops, ra[j][2], rb[j][2], ra[j][2].numel(), 0.0, lam * w_feat, 1, gl=gf) for j in range(len(ra) - 1)]
                  for (_, ra), (_, rb) in zip(rf, rr)]
         _, dx = disc._backward(rf, dtop, dfeat, False, True)
         ctx.runs = None
         return None, dx.view(ctx.shape), None, None, None
-
-
-def _loss_sum(ops, a, b, sign, mode, out, weight=1.0):
-    a = a.contiguous()
-    b = None if b is None else b.contiguous()                    # (named: the buffers must outlive the call)
-    n = a.numel()
-    npart = min(1024, (n + 255) // 256)
-    part = torch.empty(npart, dtype=torch.float64, device=a.device)
-    ops.lib.call('aero_loss_sum', _ptr(a), _ptr(b), n, C.c_float(sign), mode, _ptr(part), npart, _ptr(out), C.c_double(weight), ops.stream(a))
 
 
 def melgan_losses(disc, fake, real, n_layers=4, num_D=3, features_loss_lambda=100.0):

@@ -17,7 +17,7 @@ Every FLOP runs on the HIP kernels.  Column j of clip b of the period-p view [B,
   * conv 4 (stride 1) as a 5-tap conv on the same family; conv_post (-> 1 channel) on aero_gconv1d_fwd / _bwd;
   * LeakyReLU(0.1) behind the MFMA convs: aero_mpd_act; its derivative: aero_loss_grad mode 2; weight norm: aero_weightnorm_fwd / _bwd;
   * least-squares losses: aero_loss_sum mode 2 / aero_loss_grad mode 3; feature matching: modes 1.
-D(fake) || D(real) run once as a 2B batch and the record is kept for the critic's own step (as discriminators.Discriminator does)."""
+The cached D(fake) || D(real) pair, the critic's own step and the delivery of its gradients: aero_amd/critic.py."""
 import ctypes as C
 
 import torch
@@ -25,8 +25,8 @@ from torch import nn
 from torch.nn.utils import weight_norm
 
 from . import _lib, pack
-from .discriminators import _loss_sum, _scaled_grad
-from .engine import Ops, _ptr, _strides4
+from .critic import HipCritic, _loss_sum, _scaled_grad, _upstream
+from .engine import _ptr, _strides4
 from .modules import capture_init
 
 LRELU_SLOPE = 0.1                                                # discriminators.py:12
@@ -81,8 +81,9 @@ def stride3_images(w, bias, dev):
     return fwd, dgrad
 
 
-class MultiPeriodDiscriminator(nn.Module):
-    _supports_grad_sync = True                                   # distrib.wrap: the backward of `discriminator_loss` averages the gradients itself
+class MultiPeriodDiscriminator(HipCritic):
+    # discriminators.py:222-233: sum over periods of mean(D(fake)^2) + mean((1 - D(real))^2): (sign, mode) of aero_loss_sum, of aero_loss_grad
+    _loss_terms, _grad_terms = ((0.0, 2), (1.0, 2)), ((0.0, 3), (1.0, 3))
 
     @capture_init
     def __init__(self, hidden=32, periods=[2, 3, 5, 7, 11]):   # noqa: B006 (the reference's signature)
@@ -94,50 +95,21 @@ class MultiPeriodDiscriminator(nn.Module):
             raise ValueError(f'periods must be positive integers: {periods}')
         self.hidden = hidden
         self.discriminators = nn.ModuleList([DiscriminatorP(period, hidden=hidden) for period in periods])
-        self._ops, self._packed, self._key = None, None, None
-        self._pair, self._epoch = None, 0
-
-    def repack(self):
-        """the weights were edited behind autograd's version counters (FlatAdam's fused step): re-pack on the next forward"""
-        self._pair = None
-        self._epoch += 1
-
-    def use_library(self, lib):
-        """tests: an explicitly loaded library (the CPU-emulated test double)"""
-        self._ops = Ops(lib)
-
-    def _get_ops(self):
-        if self._ops is None:
-            self._ops = Ops(_lib.load())
-        return self._ops
 
     def _pack(self, dev):
         """weight norm of every conv (one launch each into a flat fp32 buffer), then the kernels' images of those weights"""
-        dev = torch.device(dev)
-        if dev.type == 'cuda' and dev.index is None:
-            dev = torch.device('cuda', torch.cuda.current_device())
-        key = (str(dev),) + tuple((p.data_ptr(), p._version) for p in self.parameters()) + (self._epoch,)
+        dev, key = self._pack_key(dev)
         if key == self._key:
             return self._packed
-        ops = self._get_ops()
-        convs = [conv for d in self.discriminators for conv in d.layers()]
         # a FRESH buffer per pack: an older record (a cached pair whose backward has not run yet) keeps views of the weights it was
         # computed with (conv 0's data gradient reads them), so they must not be rewritten in place under it
-        offs, n = [], 0
-        for conv in convs:
-            offs.append(n)
-            n += (conv.weight_v.numel() + 3) // 4 * 4
-        self._wflat, self._woffs = torch.empty(n, dtype=torch.float32, device=dev), offs
-        packed, k = [], 0
+        ws = iter(self._weightnorm_fwd([conv for d in self.discriminators for conv in d.layers()], dev)[1])
+        packed = []
         for d in self.discriminators:
             ents = []
             for j, conv in enumerate(d.layers()):
-                v, g = conv.weight_v.detach(), conv.weight_g.detach()
-                o = self._woffs[k]
-                k += 1
-                Cout, Cin, K = v.shape[0], v.shape[1], v.shape[2]
-                w = self._wflat[o:o + v.numel()].view(Cout, Cin, K)
-                ops.lib.call('aero_weightnorm_fwd', _ptr(v.contiguous()), _ptr(g.contiguous()), _ptr(w), Cout, Cin * K, ops.stream(w))
+                w = next(ws)
+                Cout, Cin, K = w.shape
                 b = conv.bias.detach().float().contiguous()
                 ent = dict(j=j, Cin=Cin, Cout=Cout, K=K, w=w, bias=b)
                 if j == 0:
@@ -159,14 +131,10 @@ class MultiPeriodDiscriminator(nn.Module):
         self._packed, self._key = packed, key
         return packed
 
-
     def _run(self, x):
         """x [Bt, 1, L] -> per period: dict(p, L, H, n = Bt, xf fp16 [Bt p][H], ys = [(entry, output fp16 [Bt p][rows][C], valid rows)])"""
+        self._check_input(x)
         ops = self._get_ops()
-        if not x.is_cuda and not ops.lib.is_emulator:
-            raise RuntimeError('aero_amd.mpd runs on the MI355X: move the signals to "cuda"')
-        if x.dim() != 3 or x.shape[1] != 1:
-            raise ValueError('expected a [B, 1, T] waveform')
         dev = x.device
         packed = self._pack(dev)
         Bt, L = x.shape[0], x.shape[2]
@@ -212,17 +180,6 @@ class MultiPeriodDiscriminator(nn.Module):
             out.append(dict(p=p, L=L, H=H, n=Bt, xf=xf, ys=ys))
         return out
 
-    def _run_pair(self, fake, real):
-        """D(fake) and D(real) as ONE batch of 2B signals, kept until the weights or the signals change (the critic's own step evaluates D
-        on exactly the signals and weights the generator's losses just used).  Returns (record, B)."""
-        if fake.shape != real.shape:
-            raise ValueError('fake and real must have the same shape')
-        key = (fake.data_ptr(), fake._version, real.data_ptr(), real._version, tuple(fake.shape), str(fake.device)) + \
-            tuple((p.data_ptr(), p._version) for p in self.parameters()) + (self._epoch,)
-        if self._pair is None or self._pair[0] != key:
-            self._pair = (key, self._run(torch.cat([fake.detach(), real.detach()], 0)), fake.detach(), real.detach())
-        return self._pair[1], fake.shape[0]
-
     @staticmethod
     def _half(runs, lo, hi):
         """the record of clips [lo, hi) of a run (views)"""
@@ -254,11 +211,9 @@ class MultiPeriodDiscriminator(nn.Module):
         return y_d_rs, y_d_gs, fmap_rs, fmap_gs
 
     # ------------------------------------------------------------------ losses with their HIP backward (solver.py:580-600)
-    def discriminator_loss(self, fake, real):
-        """discriminators.py:222-233 on D(real), D(fake.detach()): sum over periods of mean((1 - D(real))^2) + mean(D(fake)^2);
-        differentiable w.r.t. the critic's parameters"""
-        names, params = zip(*self.named_parameters())
-        return _MPDCriticLoss.apply(self, names, fake.detach(), real.detach(), *params)
+    def _logit_heads(self, runs, B):
+        """per period: (logits of the 2B batch fp16 [2B p][H4][1], rows of D(fake))"""
+        return [(r['ys'][-1][1], B * r['p']) for r in runs]
 
     def generator_losses(self, fake, real, features_loss_lambda=100.0):
         """solver.py:587-600: (adversarial = sum over periods of mean((1 - D(fake))^2), lambda * feature matching = lambda * the mean over
@@ -269,7 +224,7 @@ class MultiPeriodDiscriminator(nn.Module):
         """runs: record (or half of one); dtop[i]: (gradient of period i's logits fp16 [n p][H4][1], {S, 1/S}); dfeat[i][j]: the same for
         feature map j < 5 (the layer's stored buffer) or None.  Returns ({parameter name: fp32 gradient}, d waveform fp32 [n, L] or None).
         out: {name: fp32 destination} the gradients are ADDED to; gl: 0-dim fp32 device tensor, the upstream factor of the loss."""
-        from . import backward as bw, train_ops as TO
+        from . import backward as bw
         ops = self._get_ops()
         grads = {}
         dwave = None
@@ -289,8 +244,7 @@ class MultiPeriodDiscriminator(nn.Module):
                 kind, M, Cin = ent['kind'], ent['Cout'], ent['Cin']
                 need_dx = want_input or j > 0
                 if j < len(ys) - 1:
-                    f = dfeat[i][j] if dfeat is not None else None
-                    g, sc = TO.rescale_f16(ops, dx, sc, f[0], f[1]) if f is not None else TO.rescale_f16(ops, dx, sc)
+                    g, sc = self._join_feature_grad(dx, sc, dfeat, i, j)
                 prefix = f'discriminators.{i}.' + (f'convs.{j}.' if j < 5 else 'conv_post.')
                 if kind == 'post':
                     d = _lib.GconvBwdDesc()
@@ -353,90 +307,8 @@ class MultiPeriodDiscriminator(nn.Module):
                             dw_strides = (Cin, 1, M * Cin)
                         dx = ops.conv(ent['dspec'], dy4, None, N, 1, 1, Ho).view(N, Hin, Cin) if need_dx else None
                 if want_params:
-                    conv = disc.layers()[j]
-                    v, gg = conv.weight_v.detach(), conv.weight_g.detach()
-                    assert v.dtype == torch.float32 and v.is_contiguous() and gg.is_contiguous()
-                    names3 = (prefix + 'weight_g', prefix + 'weight_v', prefix + 'bias')
-                    if out is not None:
-                        dg_, dv_, dbias_ = (out[nm] for nm in names3)
-                        acc = 1
-                    else:
-                        dg_, dv_, dbias_ = torch.empty_like(gg), torch.empty_like(v), torch.empty(v.shape[0], dtype=torch.float32, device=v.device)
-                        acc = 0
-                        grads[names3[0]], grads[names3[1]], grads[names3[2]] = dg_, dv_, dbias_
-                    ops.lib.call('aero_weightnorm_bwd', _ptr(dwk), dw_strides[0], dw_strides[1], dw_strides[2], _ptr(v), _ptr(gg), _ptr(db),
-                                 sc[1:].data_ptr(), _ptr(gl), _ptr(dg_), _ptr(dv_), _ptr(dbias_), v.shape[0], v.shape[1], v.shape[2] * v.shape[3],
-                                 acc, ops.stream(v))
+                    grads.update(self._weightnorm_bwd(disc.layers()[j], prefix, dwk, dw_strides, db, sc, gl, out))
         return grads, dwave
-
-
-def _logits(r, lo, hi):
-    """period record r -> its logits of clips [lo, hi): fp16 [(hi - lo) p][H4][1] (contiguous view)"""
-    p = r['p']
-    return r['ys'][-1][1][lo * p:hi * p]
-
-
-class _MPDCriticLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, disc, names, fake, real, *params):
-        ops = disc._get_ops()
-        runs, B = disc._run_pair(fake, real)
-        loss = torch.zeros(1, dtype=torch.float64, device=fake.device)
-        for r in runs:
-            lf, lr = _logits(r, 0, B), _logits(r, B, 2 * B)
-            _loss_sum(ops, lf, None, 0.0, 2, loss, 1.0 / lf.numel())          # mean(D(fake)^2)
-            _loss_sum(ops, lr, None, 1.0, 2, loss, 1.0 / lr.numel())          # mean((1 - D(real))^2)
-        ctx.disc, ctx.names, ctx.runs, ctx.B = disc, names, runs, B
-        ctx.param_ptrs, ctx.shapes = [p.data_ptr() for p in params], [p.shape for p in params]
-        return loss[0].float()
-
-    @staticmethod
-    def backward(ctx, gl):
-        disc, ops = ctx.disc, ctx.disc._get_ops()
-        B = ctx.B
-        dtop = []
-        for r in ctx.runs:
-            full = r['ys'][-1][1]
-            g = torch.empty_like(full)
-            nh = B * r['p']
-            _, sc = _scaled_grad(ops, full[:nh], None, full[:nh].numel(), 0.0, 1.0, 3, out=g[:nh])
-            _scaled_grad(ops, full[nh:], None, full[nh:].numel(), 1.0, 1.0, 3, out=g[nh:])
-            dtop.append((g, sc))
-        glf = gl.detach().float().contiguous()
-        # distrib.wrap(critic): the mean over ranks (discriminators._CriticLoss.backward, the same protocol)
-        sync = getattr(disc, '_grad_sync', None)
-        if sync is not None and not sync.active():
-            sync = None
-        if sync is not None:
-            glf = glf * sync.mean_factor()
-        sink = getattr(disc, '_grad_sink', None)
-        sink = sink() if sink is not None else None
-        offs, n = [], 0
-        for shp in ctx.shapes:
-            offs.append(n)
-            n += (shp.numel() + 3) // 4 * 4
-        params = dict(disc.named_parameters())
-        if sink is not None and sink.accepts(ctx.param_ptrs, offs, n, glf.device) and (sync is None or sink.fresh):
-            out = {nme: params[nme].grad for nme in ctx.names}
-            sink.fresh = False
-            disc._backward(ctx.runs, dtop, None, True, False, out=out, gl=glf)
-            ctx.runs = None
-            if sync is not None:
-                sync.reduce_async(sink.flat_g)
-                sync.wait()
-            return (None, None, None, None) + (None,) * len(ctx.names)
-        total, _ = disc._backward(ctx.runs, dtop, None, True, False, gl=glf)
-        ctx.runs = None
-        if sync is not None:
-            flat = torch.cat([total[nme].reshape(-1) for nme in ctx.names])
-            sync.reduce_async(flat)
-            sync.wait()
-            o = 0
-            for nme in ctx.names:
-                k = total[nme].numel()
-                total[nme] = flat[o:o + k].view_as(total[nme])
-                o += k
-        return (None, None, None, None) + tuple(total[nm] for nm in ctx.names)
 
 
 class _MPDGeneratorLoss(torch.autograd.Function):
@@ -463,7 +335,7 @@ class _MPDGeneratorLoss(torch.autograd.Function):
         disc, ops = ctx.disc, ctx.disc._get_ops()
         rf, rr = ctx.runs
         lam, npairs = ctx.cfg
-        ga, gf = gadv.detach().float().contiguous(), gfeat.detach().float().contiguous()
+        ga, gf = _upstream(gadv), _upstream(gfeat)
         dtop = [_scaled_grad(ops, a['ys'][-1][1], None, a['ys'][-1][1].numel(), 1.0, 1.0, 3, gl=ga) for a in rf]
         dfeat = [[_scaled_grad(ops, ya, yb, a['n'] * a['p'] * Ho * e['Cout'], 0.0, lam / npairs, 1, gl=gf)
                   for (e, ya, Ho), (_, yb, _) in zip(a['ys'][:-1], b['ys'][:-1])] + [None] for a, b in zip(rf, rr)]

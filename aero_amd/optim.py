@@ -19,6 +19,16 @@ import torch
 from . import _lib
 
 
+def flat_offsets(sizes):
+    """the layout of a flat fp32 buffer holding tensors of these sizes: every tensor starts on a 16-byte boundary (4 floats: the kernels
+    move float4).  Returns (offsets, total length).  `FlatAdam.accepts` compares a backward's layout against this one."""
+    offs, n = [], 0
+    for sz in sizes:
+        offs.append(n)
+        n += (sz + 3) // 4 * 4
+    return offs, n
+
+
 class FlatAdam:
     def __init__(self, params, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, lib=None, model=None):
         """model: the `Aero` module these parameters belong to (optional), or a list of modules (the chained critics of train.py:91-96).
@@ -35,11 +45,7 @@ class FlatAdam:
         self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
         self.lib = lib
         sizes = [p.numel() for p in self.params]
-        # every parameter starts on a 16-byte boundary of the flat buffer (4 floats): the kernel moves float4
-        offs, n = [], 0
-        for sz in sizes:
-            offs.append(n)
-            n += (sz + 3) // 4 * 4
+        offs, n = flat_offsets(sizes)
         self.n = n
         self.flat_p = torch.zeros(n, dtype=torch.float32, device=dev)
         self.flat_g = torch.zeros(n, dtype=torch.float32, device=dev)

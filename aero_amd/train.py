@@ -25,6 +25,7 @@ import torch
 from . import _lib, backward as bw, pack, train_ops as TO
 from ._lib import ACT_GELU, ACT_GLU, ACT_NONE, ACT_RELU, ACT_SNAKE
 from .engine import Ops, _hann_padded, blstm_frames
+from .optim import flat_offsets
 
 GRAD_TARGET = 64.0          # a stage's input gradient has its largest magnitude in [32, 64]: three orders of magnitude of headroom
                             # to the fp16 maximum for growth inside the stage, six down to the smallest normal number
@@ -921,10 +922,7 @@ class AeroFunction(torch.autograd.Function):
     def backward(ctx, dy, _dspec, _dlr):
         eng = ctx.engine
         dev = dy.device
-        offs, n = [], 0
-        for s in ctx.shapes:
-            offs.append(n)
-            n += (s.numel() + 3) // 4 * 4
+        offs, n = flat_offsets(s.numel() for s in ctx.shapes)
         # FlatAdam (aero_amd/optim.py) keeps every parameter's .grad as a view of ONE flat buffer with this same layout: the backward
         # then works IN that buffer (freshly zeroed by zero_grad) and hands autograd no per-parameter gradients at all -- its
         # AccumulateGrad nodes were ~300 little `grad += g` launches per step; a buffer that already holds gradients gets one flat add

@@ -90,29 +90,25 @@ class TrainStep:
         if self.mrstft is not None:
             sc, mag = self.mrstft(pr.squeeze(1), hr.squeeze(1))
             out['generator']['stft'] = sc + mag
-        if self.adversarial and 'msd_melgan' in self.dmodels:
-            exp = self.args.experiment
-            critic = self.dmodels['msd_melgan']
-            md = exp.melgan_discriminator
-            if md.num_D != critic.num_D:
-                raise ValueError('melgan_discriminator.num_D does not match the critic')
-            adv, feat = critic.generator_losses(pr, hr, n_layers=md.n_layers, features_loss_lambda=exp.features_loss_lambda)
+        exp = self.args.experiment
+        # (this order fixes the order in which the generator's terms are summed, and with it the fp32 total)
+        for name, tag in (('msd_melgan', 'melgan'), ('mpd', 'mpd')):
+            if not self.adversarial or name not in self.dmodels:
+                continue
+            critic, kw = self.dmodels[name], {}
+            if name == 'msd_melgan':
+                md = exp.melgan_discriminator
+                if md.num_D != critic.num_D:
+                    raise ValueError('melgan_discriminator.num_D does not match the critic')
+                kw['n_layers'] = md.n_layers
+            adv, feat = critic.generator_losses(pr, hr, features_loss_lambda=exp.features_loss_lambda, **kw)   # solver.py:498-520,587-600
             if not exp.get('only_features_loss'):
-                out['generator']['adversarial_melgan'] = adv
+                out['generator']['adversarial_' + tag] = adv
             if not exp.get('only_adversarial_loss'):
-                out['generator']['features_melgan'] = feat
+                out['generator']['features_' + tag] = feat
             # D(fake.detach()), D(real) on the weights the generator's losses just used (solver.py:478-480): the critic keeps that
             # record, so this costs no second forward
-            out['discriminator']['msd_melgan'] = critic.discriminator_loss(pr.detach(), hr)
-        if self.adversarial and 'mpd' in self.dmodels:                        # solver.py:457-463,580-600
-            exp = self.args.experiment
-            mpd = self.dmodels['mpd']
-            adv, feat = mpd.generator_losses(pr, hr, features_loss_lambda=exp.features_loss_lambda)
-            if not exp.get('only_features_loss'):
-                out['generator']['adversarial_mpd'] = adv
-            if not exp.get('only_adversarial_loss'):
-                out['generator']['features_mpd'] = feat
-            out['discriminator']['mpd'] = mpd.discriminator_loss(pr.detach(), hr)
+            out['discriminator'][name] = critic.discriminator_loss(pr.detach(), hr)
         return out
 
     def __call__(self, lr, hr):

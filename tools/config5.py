@@ -2,6 +2,7 @@
 forward -> multi-resolution STFT loss -> backward -> FlatAdam.step.  usage: config5.py [B] [steps] [--gan] [--mpd]
 (--gan: + the msd_melgan critic; --mpd: + msd_melgan AND the multi-period critic mpd at the reference's width, both in one critic Adam as
 train.py:91-96 chains them; every step prints its whole time, `step ms`)"""
+import functools
 import os
 import sys
 import time
@@ -27,17 +28,15 @@ def main():
     model = Aero(**dict(args.experiment.aero)).cuda().train()
     opt = FlatAdam(model.parameters(), lr=3e-4, betas=(0.9, 0.999), model=model)
     crit = losses.MultiResolutionSTFTLoss(factor_sc=0.5, factor_mag=0.5)                  # main_config.yaml:64-65
-    disc = opt_d = None
+    critics, opt_d = [], None                                   # (log tag, critic, its generator_losses keywords)
     if gan:
         from aero_amd.discriminators import Discriminator
-        disc = Discriminator(num_D=3, ndf=16, n_layers=4, downsampling_factor=4).cuda()
-        mpd = None
+        critics.append(('', Discriminator(num_D=3, ndf=16, n_layers=4, downsampling_factor=4).cuda(), dict(n_layers=4)))
         if use_mpd:
             from aero_amd.mpd import MultiPeriodDiscriminator
-            mpd = MultiPeriodDiscriminator().cuda()
-            opt_d = FlatAdam(list(disc.parameters()) + list(mpd.parameters()), lr=3e-4, betas=(0.9, 0.999), model=[disc, mpd])
-        else:
-            opt_d = FlatAdam(disc.parameters(), lr=3e-4, betas=(0.9, 0.999), model=disc)
+            critics.append(('_mpd', MultiPeriodDiscriminator().cuda(), {}))
+        ds = [d for _, d, _ in critics]
+        opt_d = FlatAdam([p for d in ds for p in d.parameters()], lr=3e-4, betas=(0.9, 0.999), model=ds[0] if len(ds) == 1 else ds)
     g = torch.Generator().manual_seed(0)
     lr = torch.randn(B, 1, 110250, generator=g).cuda()
     hr = (0.1 * torch.randn(B, 1, 441000, generator=g)).cuda()
@@ -50,14 +49,10 @@ def main():
         sc, mg = crit(y.squeeze(1), hr.squeeze(1))
         loss = sc + mg
         extra = ''
-        if gan:
-            adv, feat = disc.generator_losses(y, hr, n_layers=4, features_loss_lambda=100.0)      # solver.py:498-520
+        for tag, d, kw in critics:
+            adv, feat = d.generator_losses(y, hr, features_loss_lambda=100.0, **kw)                  # solver.py:498-520,587-600
             loss = loss + adv + feat
-            extra = f' adv {float(adv.detach()):.4f} feat {float(feat.detach()):.4f}'
-            if use_mpd:
-                adv_p, feat_p = mpd.generator_losses(y, hr, features_loss_lambda=100.0)               # solver.py:587-600
-                loss = loss + adv_p + feat_p
-                extra += f' adv_mpd {float(adv_p.detach()):.4f} feat_mpd {float(feat_p.detach()):.4f}'
+            extra += f' adv{tag} {float(adv.detach()):.4f} feat{tag} {float(feat.detach()):.4f}'
         opt.zero_grad()
         loss.backward()
         torch.cuda.synchronize()
@@ -67,9 +62,7 @@ def main():
         t3 = time.time()
         td = 0.0
         if gan:                                                  # solver.py:607-611: the critic's own step on the detached prediction
-            d_loss = disc.discriminator_loss(y.detach(), hr)
-            if use_mpd:
-                d_loss = d_loss + mpd.discriminator_loss(y.detach(), hr)
+            d_loss = functools.reduce(torch.add, [d.discriminator_loss(y.detach(), hr) for _, d, _ in critics])
             opt_d.zero_grad()
             d_loss.backward()
             opt_d.step()
