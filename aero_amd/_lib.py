@@ -133,6 +133,17 @@ class Enc0Desc(C.Structure):
                 ('pad', i32), ('act', i32)]
 
 
+class SeanetConvDesc(C.Structure):
+    _fields_ = [('x', vp), ('wimg', vp), ('bias', fp), ('add', vp), ('y', vp),
+                ('B', i32), ('Tin', i32), ('Cin', i32), ('Tq', i32), ('M', i32), ('K', i32), ('stride', i32), ('dil', i32), ('pad', i32),
+                ('reflect', i32), ('ksteps', i32), ('R', i32), ('P', i32), ('Tout', i32), ('Cout', i32), ('act', i32), ('in_slope', C.c_float)]
+
+
+class SeanetResDesc(C.Structure):
+    _fields_ = [('x', vp), ('w1', vp), ('w2s', vp), ('b1', fp), ('b2s', fp), ('add', vp), ('y', vp),
+                ('B', i32), ('T', i32), ('C', i32), ('d', i32), ('ks1', i32), ('ks2', i32), ('slope', C.c_float)]
+
+
 DCONV_MAX_DEPTH = 4
 
 
@@ -232,6 +243,12 @@ _PROTOS = {
     'aero_mpd_conv0_slabs': (i32, [i32, i32]),
     'aero_mpd_conv0_bwd': (i32, [vp, vp, fp, fp, fp, fp, i32, fp, fp, i32, i32, i32, i32, vp]),
     'aero_mpd_act': (i32, [vp, i32, i32, i32, i32, C.c_float, vp]),
+    'aero_seanet_stats': (i32, [fp, i32, i32, C.c_float, fp, vp]),
+    'aero_seanet_front': (i32, [fp, fp, fp, fp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    'aero_seanet_conv_in': (i32, [fp, fp, fp, vp, i32, i32, i32, vp]),
+    'aero_seanet_conv': (i32, [C.POINTER(SeanetConvDesc), vp]),
+    'aero_seanet_resblock': (i32, [C.POINTER(SeanetResDesc), vp]),
+    'aero_seanet_conv_out': (i32, [vp, vp, fp, fp, fp, fp, i32, i32, i32, i32, C.c_float, vp]),
 }
 
 EXPORTS = tuple(_PROTOS)

@@ -3,7 +3,7 @@
 // translation unit against a CPU emulation of the HIP subset, as a test double -- never loaded by
 // the product.)
 //
-// Built by __graft_entry__.build():  hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c -DAERO_PART=k  for k = 0..8 (no 5), IN PARALLEL,
+// Built by __graft_entry__.build():  hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c -DAERO_PART=k  for k = 0..9 (no 5), IN PARALLEL,
 // then one link into aero_amd/libaero_hip.so.  The library is ONE source file cut into six independently compiled parts (each
 // kernel header belongs to exactly one part; a part holds the entry points over its kernels): as a single translation unit it took
 // four minutes to compile; now a change to one header rebuilds one part.  Without -DAERO_PART (the emulator's build) the file is the
@@ -46,6 +46,9 @@
 #endif
 #if AERO_IN(8)
 #include "k_mpd.h"
+#endif
+#if AERO_IN(9)
+#include "k_seanet.h"
 #endif
 
 #include <stdio.h>
@@ -813,3 +816,47 @@ int aero_mpd_act(void* y, int32_t N, int32_t H, int32_t pitch, int32_t C, float 
 }
 
 #endif  // part 8
+
+// ---------------------------------------------------------------------------------------------------------------
+// part 9 -- the Seanet baseline generator (k_seanet.h; seanet.py)
+#if AERO_IN(9)
+
+int aero_seanet_stats(const float* x, int32_t B, int32_t L, float floor_, float* stats, void* stream) {
+    const char* err = "";
+    int rc = aero_seanet_stats_launch(x, B, L, floor_, stats, (hipStream_t)stream, &err);
+    return aero_finish(rc, err);
+}
+
+int aero_seanet_front(const float* x, const float* stats, const float* table, float* y, int32_t B, int32_t L, int32_t Lup, int32_t Tpad, int32_t og,
+                      int32_t nw, int32_t width, void* stream) {
+    const char* err = "";
+    int rc = aero_seanet_front_launch(x, stats, table, y, B, L, Lup, Tpad, og, nw, width, (hipStream_t)stream, &err);
+    return aero_finish(rc, err);
+}
+
+int aero_seanet_conv_in(const float* x, const float* w, const float* bias, void* y, int32_t B, int32_t T, int32_t C, void* stream) {
+    const char* err = "";
+    int rc = aero_seanet_conv_in_launch(x, w, bias, y, B, T, C, (hipStream_t)stream, &err);
+    return aero_finish(rc, err);
+}
+
+int aero_seanet_conv(const aero_seanet_conv_desc* d, void* stream) {
+    const char* err = "";
+    int rc = aero_seanet_conv_launch(d, (hipStream_t)stream, &err);
+    return aero_finish(rc, err);
+}
+
+int aero_seanet_resblock(const aero_seanet_res_desc* d, void* stream) {
+    const char* err = "";
+    int rc = aero_seanet_resblock_launch(d, (hipStream_t)stream, &err);
+    return aero_finish(rc, err);
+}
+
+int aero_seanet_conv_out(const void* x, const void* w, const float* bias, const float* skip, const float* stats, float* y, int32_t B, int32_t T,
+                         int32_t C, int32_t Tout, float slope, void* stream) {
+    const char* err = "";
+    int rc = aero_seanet_conv_out_launch(x, w, bias, skip, stats, y, B, T, C, Tout, slope, (hipStream_t)stream, &err);
+    return aero_finish(rc, err);
+}
+
+#endif  // part 9

@@ -154,8 +154,15 @@ def load_generator(args, device='cuda'):
     by the reference's serializer ({'models': {'generator': {'state': ...}}, 'best_states': ..., 'args': ...}).
     Like the reference (torch.load on a missing path raises), a configured but absent checkpoint is an error; random
     weights are only used when the caller says so (`+random_init=true`), e.g. for plumbing runs and benchmarks."""
-    from .modules import Aero
-    model = Aero(**args.experiment.aero)
+    name = args.experiment.get('model', 'aero')                  # modelFactory.py:7-10
+    if name == 'seanet':
+        from .seanet import Seanet
+        model = Seanet(**args.experiment.seanet)
+    elif name == 'aero':
+        from .modules import Aero
+        model = Aero(**args.experiment.aero)
+    else:
+        raise NotImplementedError(f"model '{name}': the generators implemented on MI355X are aero and seanet")
     ckpt = args.get('checkpoint_file')
     if args.get('random_init'):
         return model.to(device).eval()

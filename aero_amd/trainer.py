@@ -17,16 +17,21 @@ from .optim import FlatAdam
 
 
 def build_models(args):
-    """modelFactory.py:6-29 for what aero's experiment files use: `model: aero` and, with `adversarial: true`, the critics of
+    """modelFactory.py:6-29 for what the experiment files use: `model: aero` or `model: seanet` (the time-domain baseline, kwargs from
+    `experiment.seanet`; inference only, aero_amd/seanet.py) and, with `adversarial: true`, the critics of
     `discriminator_models`: the MelGAN multi-scale critic `msd_melgan` and the HiFi-GAN multi-period critic `mpd`, constructed in
     modelFactory.py's fixed order (msd_melgan, then mpd) whatever the list order, so a seed draws the reference's initial weights.
     `mpd` takes its kwargs from `experiment.mpd`; without that block the constructor's defaults are used (the reference would fail on the
-    missing key).  Seanet and the critics `msd_hifi` / `hifi` stay NotImplementedError: the reference cannot run them either."""
-    from .modules import Aero
+    missing key).  The critics `msd_hifi` / `hifi` stay NotImplementedError: the reference cannot run them either."""
     exp = args.experiment
-    if exp.model != 'aero':
-        raise NotImplementedError(f"model '{exp.model}': only the AERO generator is implemented on MI355X")
-    models = {'generator': Aero(**dict(exp.aero))}
+    if exp.model == 'aero':
+        from .modules import Aero
+        models = {'generator': Aero(**dict(exp.aero))}
+    elif exp.model == 'seanet':
+        from .seanet import Seanet
+        models = {'generator': Seanet(**dict(exp.seanet))}
+    else:
+        raise NotImplementedError(f"model '{exp.model}': the generators implemented on MI355X are aero and seanet")
     if exp.get('adversarial'):
         names = list(exp.discriminator_models)
         for name in names:

@@ -633,6 +633,52 @@ int aero_mpd_conv0_bwd(const void* dyp, const void* x, const float* w, const flo
                        float* db, int32_t N, int32_t H, int32_t C, int32_t pitch, void* stream);
 int aero_mpd_act(void* y, int32_t N, int32_t H, int32_t pitch, int32_t C, float slope, void* stream);
 
+/* Seanet baseline generator, inference forward (reference src/models/seanet.py; csrc/k_seanet.h; aero_amd/seanet.py).  Activations fp16
+ * channels-last [B][T][C]; the waveform ends fp32.
+ *   aero_seanet_stats     x fp32 [B][L] -> stats fp32 [B][2] = {unbiased std, 1 / (floor + std)} per item
+ *   aero_seanet_front     y fp32 [B][Tpad]: y[t] = inv * sum_k table[t % nw][k] x[(t / nw) og - width + k] for t < Lup (the polyphase form of
+ *                         torchaudio.functional.resample: table fp32 [nw][2 width + og], og / nw the reduced rates), 0 for Lup <= t < Tpad;
+ *                         table NULL: y = inv * x (Lup = L); stats NULL: inv = 1
+ *   aero_seanet_conv_in   ReflectionPad1d(3) + Conv1d(1, C, 7) + tanh: x fp32 [B][T] (rounded to fp16 as read), w fp32 [C][7], y fp16 [B][T][C]
+ *   aero_seanet_conv      the general MFMA conv (descriptor below)
+ *   aero_seanet_resblock  ResnetBlock(C, dilation d) in one launch (descriptor below)
+ *   aero_seanet_conv_out  LeakyReLU(slope) + ReflectionPad1d(3) + Conv1d(C, 1, 7) + tanh, + skip fp32 [B][T] (may be NULL), the first Tout
+ *                         steps, times stats[b][0] (stats may be NULL): x fp16 [B][T][C], w fp16 [7][C], y fp32 [B][Tout]
+ * Weight images (wimg, w1, w2s): fp16 [ceil(M / 32) * 2][ksteps][64][8], element (tile, ks, lane, e) = W[16 tile + (lane & 15)][32 ks + 8 (lane >> 4) + e]
+ * of the [M][K Cin] matrix (column k Cin + c), zero padded. */
+typedef struct {
+    const void* x;            /* fp16 [B][Tin][Cin] */
+    const void* wimg;         /* image of W [M][K Cin] */
+    const float* bias;        /* [M] */
+    const void* add;          /* fp16 [B][Tout][Cout] added behind the activation, or NULL */
+    void* y;                  /* fp16 [B][Tout][Cout] */
+    int32_t B, Tin, Cin, Tq, M, K, stride, dil, pad, reflect, ksteps;
+    /* row q < Tq of the product reads x[q stride + k dil - pad] (zero or reflect padded); its value m = ph Cout + co goes to time
+     * q R + ph - P (if inside [0, Tout)), channel co: R = 1, P = 0 for a conv, R = the stride for a transposed conv (K = 2 taps) */
+    int32_t R, P, Tout, Cout;
+    int32_t act;              /* 0 none, 1 tanh */
+    float in_slope;           /* LeakyReLU on the input as it is read (1 = none) */
+} aero_seanet_conv_desc;
+typedef struct {
+    const void* x;            /* fp16 [B][T][C] */
+    const void* w1;           /* image of [C][3 C]: the dilated k = 3 conv, column k C + c */
+    const void* w2s;          /* image of [C][2 C]: [W2 | Ws] */
+    const float* b1;          /* [C] */
+    const float* b2s;         /* [C]: b2 + bs */
+    const void* add;          /* fp16 [B][T][C] added to the result, or NULL */
+    void* y;                  /* fp16 [B][T][C], not x */
+    int32_t B, T, C, d, ks1, ks2;
+    float slope;
+} aero_seanet_res_desc;
+int aero_seanet_stats(const float* x, int32_t B, int32_t L, float floor_, float* stats, void* stream);
+int aero_seanet_front(const float* x, const float* stats, const float* table, float* y, int32_t B, int32_t L, int32_t Lup, int32_t Tpad, int32_t og,
+                      int32_t nw, int32_t width, void* stream);
+int aero_seanet_conv_in(const float* x, const float* w, const float* bias, void* y, int32_t B, int32_t T, int32_t C, void* stream);
+int aero_seanet_conv(const aero_seanet_conv_desc* d, void* stream);
+int aero_seanet_resblock(const aero_seanet_res_desc* d, void* stream);
+int aero_seanet_conv_out(const void* x, const void* w, const float* bias, const float* skip, const float* stats, float* y, int32_t B, int32_t T,
+                         int32_t C, int32_t Tout, float slope, void* stream);
+
 /* RCCL over xGMI behind the same ABI (replaces the NCCL process group of the reference's src/ddp/distrib.py:16-34 for a
  * host that is not PyTorch).  One communicator per process, one process per GPU (hipSetDevice first).  Rank 0 calls aero_comm_unique_id
  * and hands the 128 bytes to the other ranks by any host channel; every rank then calls aero_comm_init with the same bytes.
