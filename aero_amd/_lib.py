@@ -157,6 +157,11 @@ class DconvDesc(C.Structure):
                 ('F', i32), ('eps', C.c_float), ('layer', DconvLayer * DCONV_MAX_DEPTH)]
 
 
+class DconvRewriteDesc(C.Structure):
+    _fields_ = [('dconv', DconvDesc), ('rw_w', vp), ('rw_bias', fp), ('post_add', fp),
+                ('dst', vp), ('d_b', i64), ('d_f', i64), ('d_t', i64)]
+
+
 _PROTOS = {
     'aero_version': (C.c_char_p, []),
     'aero_last_error': (C.c_char_p, []),
@@ -197,6 +202,8 @@ _PROTOS = {
     'aero_enc0_fwd': (i32, [C.POINTER(Enc0Desc), vp]),
     'aero_dconv_row_fwd': (i32, [C.POINTER(DconvDesc), vp]),
     'aero_dconv_row_fits': (i32, [i32, i32, i32, i32]),
+    'aero_dconv_row_rewrite_fwd': (i32, [C.POINTER(DconvRewriteDesc), vp]),
+    'aero_dconv_row_rewrite_fits': (i32, [i32, i32, i32, i32]),
     'aero_lstm_bwd': (i32, [C.POINTER(LstmBwdDesc), vp]),
     'aero_lstm_bwd_k4p': (i32, [i32]),
     'aero_localstate_bwd': (i32, [C.POINTER(AttnBwdDesc), vp]),

@@ -469,11 +469,20 @@ int aero_freqfc_fwd(const aero_freqfc_desc* d, void* stream) {
 
 int aero_dconv_row_fwd(const aero_dconv_desc* d, void* stream) {
     const char* err = "";
-    int rc = aero_dconv_launch(d, (hipStream_t)stream, &err);
+    int rc = aero_dconv_launch(d, nullptr, (hipStream_t)stream, &err);
     return aero_finish(rc, err);
 }
 
 int aero_dconv_row_fits(int T, int C, int hidden, int max_dilation) { return aero_dconv_row_fits_impl(T, C, hidden, max_dilation); }
+
+int aero_dconv_row_rewrite_fwd(const aero_dconv_rewrite_desc* d, void* stream) {
+    const char* err = "";
+    if (!d) return aero_fail(AERO_ERR_ARG, "dconv rewrite: null descriptor");
+    int rc = aero_dconv_launch(&d->dconv, d, (hipStream_t)stream, &err);
+    return aero_finish(rc, err);
+}
+
+int aero_dconv_row_rewrite_fits(int T, int C, int hidden, int max_dilation) { return aero_dconv_row_fits_impl(T, C, hidden, max_dilation, true); }
 
 int aero_enc0_fwd(const aero_enc0_desc* d, void* stream) {
     const char* err = "";

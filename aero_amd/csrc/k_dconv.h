@@ -19,6 +19,12 @@
 // Block-wide reductions: wave shuffles + NW partials in LDS.  HBM traffic: 4*C bytes per (row, time step); the kernel
 // itself is bound by the LDS pipe and the VALU (PMC of the first version: LDS pipe 74-85 % busy, half of it bank
 // conflicts on the W2 fragments and the h side buffer -- hence W2 in lane order and h in registers).
+//
+// RW = true (aero_dconv_row_rewrite_fwd): the encoder's rewrite conv + GLU (+ frequency embedding row) that follows the branch where no
+// GroupNorm sits between them (aero.py:133, 475-480) runs as a TAIL PASS on the finished row instead of a second kernel that reads the
+// row back from HBM: r = W_rw . x[t,:] + b_rw as MFMAs (2C rows, K = C; B operand straight from the row image as in pass A, W_rw staged
+// once per block in the LDS the last layer's weights and constants leave free, rows GLU-interleaved as W2), a * sigmoid(b) + emb[f, :],
+// fp16 in place into the row image, which is then written to the OUTPUT tensor; the DConv output itself never reaches HBM.
 #pragma once
 #include "aero_common.h"
 
@@ -28,6 +34,11 @@ struct AeroDconvK {
     int logp;     // 16 pad bytes after every (1 << logp) rows of the row image: b128 reads of 16 consecutive rows conflict-free
     int T16;      // T rounded up to 16
     int PADR;     // zero rows before t = 0 and after T16 (largest dilation, rounded up to 8 rows: fragment rows stay bank-aligned)
+    // rewrite tail (RW instantiations only)
+    const void* rw_w;         // fp16 [C/8][ceil(C/32)][64 lanes][8]: 16x16x32 A fragments of the GLU-interleaved W_rw in lane order, zero beyond C
+    const float* rw_b;        // [2C] GLU-interleaved
+    const float* rw_add;      // [F][C] or NULL
+    void* out; int64_t o_b, o_f, o_t;
 };
 
 static inline int aero_dconv_logp(int C) {
@@ -51,6 +62,16 @@ static inline size_t aero_dconv_lds_bytes(int T, int C, int hidden, int maxdil) 
     return halves * 2 + floats * 4;
 }
 
+// ... with the rewrite tail: W_rw [2C][roundup(C, 32)] fp16 + b_rw [2C] + emb row [C] take the place of the last layer's weights and constants
+static inline size_t aero_dconv_rw_lds_bytes(int T, int C, int hidden, int maxdil) {
+    const size_t base = aero_dconv_lds_bytes(T, C, hidden, maxdil);
+    if (!base || C % 16) return 0;
+    const int T16 = (T + 15) / 16 * 16, padr = (maxdil + 7) / 8 * 8, xrows = T16 + 2 * padr;
+    const size_t xbytes = ((size_t)xrows * C + (size_t)((xrows >> aero_dconv_logp(C)) + 1) * 8) * 2;
+    const size_t tail = (size_t)2 * C * ((C + 31) / 32 * 32) * 2 + (size_t)3 * C * 4;
+    return xbytes + (base - xbytes > tail ? base - xbytes : tail);
+}
+
 // (sum, sum of squares) of a row -> mean and 1/sqrt(var + eps).  fp64 only for the cancellation-prone E[x^2] - mean^2; a float rsqrt
 // with one Newton step instead of a double division and square root (those expand to ~100 instructions each, and EVERY thread
 // of the block runs them twice per layer: the first version spent 15 % of its vector instructions there)
@@ -69,7 +90,7 @@ static inline int aero_dconv_nw(size_t lds_bytes, int T) { return (lds_bytes > 8
 
 // HM = HP/16: M fragments of conv1 = k-steps of conv2;  NF2 = C/8 = M fragments of conv2;  NW waves, each owning at most MAXF
 // 16-step column fragments (cf = wave + f*NW): T <= 16 * NW * MAXF
-template <int HM, int NF2, int NW, int MAXF>
+template <int HM, int NF2, int NW, int MAXF, bool RW = false>
 __global__ __launch_bounds__(NW * 64, 4) void aero_dconv_row_kernel(AeroDconvK p) {     // 4 waves per SIMD: <= 128 registers (two 8-wave blocks per CU)
     constexpr int C = NF2 * 8, HP = HM * 16, NK1 = (3 * C + 31) / 32, K1p = NK1 * 32, CU = NF2, NT = NW * 64;
     const aero_dconv_desc& d = p.d;
@@ -282,25 +303,74 @@ __global__ __launch_bounds__(NW * 64, 4) void aero_dconv_row_kernel(AeroDconvK p
             }
         }
     }
+    if constexpr (RW) {
+        // ---- tail: rewrite conv (2C GLU-interleaved rows, K = C) + GLU + embedding row, fp16 in place into the row image
+        constexpr int NKR = (C + 31) / 32, KR = NKR * 32;        // k-steps of 16x16x32; W_rw is zero beyond C, and so is the B operand.  (One
+        // 16x16x16 step for C % 32 == 16 behind the 16x16x32 ones returned stale accumulator rows on the device: every step has one shape.)
+        h16* wr = w1s;                                           // [NF2][NKR][64 lanes][8]
+        float* rb = (float*)(wr + 2 * C * KR);                   // [2C]
+        float* re = rb + 2 * C;                                  // [C]
+        __syncthreads();                                         // every wave is done with the last layer's weights and constants
+        for (int ub = wave * 64; ub < 2 * C * KR / 8; ub += NT)
+            if (ub + lane < 2 * C * KR / 8) aero_glds16((const h16*)p.rw_w + (ub + lane) * 8, wr + ub * 8);
+        for (int ub = wave * 64; ub < 2 * C / 4; ub += NT)
+            if (ub + lane < 2 * C / 4) aero_glds16((const h16*)(p.rw_b + (ub + lane) * 4), (h16*)rb + ub * 8);
+        for (int ub = wave * 64; ub < C / 4; ub += NT)
+            if (ub + lane < C / 4) aero_glds16(p.rw_add ? (const h16*)(p.rw_add + (int64_t)(row % d.F) * C + (ub + lane) * 4) : aero_zero_page, (h16*)re + ub * 8);
+        __syncthreads();                                         // (drains the copies: vmcnt)
+        // a wave's B operands of ALL its fragments first: the results overwrite the rows they were read from
+        h16x8 xb[MAXF][NKR];
+        int xrow[MAXF];
+#pragma unroll
+        for (int f = 0; f < MAXF; ++f) {
+            const int cf = wave + f * NW;
+            xrow[f] = xoff((cf < nfrag ? cf : 0) * 16 + col + p.PADR);
+#pragma unroll
+            for (int ks = 0; ks < NKR; ++ks) {
+                xb[f][ks] = (h16x8){0, 0, 0, 0, 0, 0, 0, 0};
+                if (ks * 32 + 24 < C || ks * 32 + g * 8 < C) xb[f][ks] = *(const h16x8*)&xs[xrow[f] + ks * 32 + g * 8];
+            }
+        }
+#pragma unroll
+        for (int mf = 0; mf < NF2; ++mf) {
+            const f32x4 bias = *(const f32x4*)&rb[mf * 16 + g * 4];
+            const f32x2 pe = *(const f32x2*)&re[mf * 8 + g * 2];
+            h16x8 wa[NKR];
+#pragma unroll
+            for (int ks = 0; ks < NKR; ++ks) wa[ks] = *(const h16x8*)&wr[(mf * NKR + ks) * 512 + lane * 8];
+#pragma unroll
+            for (int f = 0; f < MAXF; ++f) {
+                if (wave + f * NW >= nfrag) continue;
+                f32x4 v = bias;
+#pragma unroll
+                for (int ks = 0; ks < NKR; ++ks) v = __builtin_amdgcn_mfma_f32_16x16x32_f16(wa[ks], xb[f][ks], v, 0, 0, 0);
+                constexpr float NL2E = -1.4426950408889634f;
+                const float g0 = aero_rcp(1.f + aero_exp2(v[1] * NL2E)), g1 = aero_rcp(1.f + aero_exp2(v[3] * NL2E));
+                *(h16x2*)&xs[xrow[f] + mf * 8 + g * 2] = (h16x2){(h16)fmaf(v[0], g0, pe[0]), (h16)fmaf(v[2], g1, pe[1])};
+            }
+        }
+    }
     __syncthreads();
     {
-        h16* dst = (h16*)d.y + (int64_t)row * T * C;
+        h16* dst = RW ? (h16*)p.out + (int64_t)(row / d.F) * p.o_b + (int64_t)(row % d.F) * p.o_f : (h16*)d.y + (int64_t)row * T * C;
+        const int64_t dt = RW ? p.o_t : (int64_t)C;
         for (int u = tid; u < T * CU; u += NT) {
             const int t = u / CU, s = u - t * CU;
-            *(h16x8*)(dst + (int64_t)t * C + s * 8) = *(const h16x8*)&xs[xoff(t + p.PADR) + s * 8];
+            *(h16x8*)(dst + (int64_t)t * dt + s * 8) = *(const h16x8*)&xs[xoff(t + p.PADR) + s * 8];
         }
     }
 }
 
-static int aero_dconv_row_fits_impl(int T, int C, int hidden, int maxdil) {
-    const size_t b = aero_dconv_lds_bytes(T, C, hidden, maxdil);
+static int aero_dconv_row_fits_impl(int T, int C, int hidden, int maxdil, bool rw = false) {
+    const size_t b = rw ? aero_dconv_rw_lds_bytes(T, C, hidden, maxdil) : aero_dconv_lds_bytes(T, C, hidden, maxdil);
     const int nf2 = C / 8;
     const bool inst = nf2 == 2 || nf2 == 4 || nf2 == 6 || nf2 == 8 || nf2 == 12 || nf2 == 16;      // instantiated widths
     return b != 0 && b <= 160 * 1024 && inst && T <= (nf2 >= 12 && aero_dconv_nw(b, T) == 16 ? 512 : 1024);
 }
 
-static int aero_dconv_launch(const aero_dconv_desc* d, hipStream_t stream, const char** err) {
-    if (!d || !d->x || !d->y) { *err = "dconv: null pointer"; return AERO_ERR_ARG; }
+// rw: the rewrite tail of aero_dconv_row_rewrite_fwd (NULL: the plain branch, rows written to d->y)
+static int aero_dconv_launch(const aero_dconv_desc* d, const aero_dconv_rewrite_desc* rw, hipStream_t stream, const char** err) {
+    if (!d || !d->x || (!rw && !d->y)) { *err = "dconv: null pointer"; return AERO_ERR_ARG; }
     if (d->R < 1 || d->T < 1 || d->depth < 1 || d->depth > AERO_DCONV_MAX_DEPTH || d->F < 1) { *err = "dconv: bad geometry"; return AERO_ERR_ARG; }
     if (d->act != AERO_ACT_RELU && d->act != AERO_ACT_GELU && d->act != AERO_ACT_SNAKE && d->act != AERO_ACT_NONE) { *err = "dconv: unsupported act"; return AERO_ERR_UNSUPPORTED; }
     int maxdil = 1;
@@ -312,8 +382,14 @@ static int aero_dconv_launch(const aero_dconv_desc* d, hipStream_t stream, const
         if ((((uintptr_t)L.w1 | (uintptr_t)L.w2 | (uintptr_t)L.consts) & 15)) { *err = "dconv: unaligned weights"; return AERO_ERR_ARG; }
         maxdil = L.dilation > maxdil ? L.dilation : maxdil;
     }
-    if ((((uintptr_t)d->x | (uintptr_t)d->y) & 15)) { *err = "dconv: unaligned rows"; return AERO_ERR_ARG; }
-    if (!aero_dconv_row_fits_impl(d->T, d->C, d->hidden, maxdil)) { *err = "dconv: row does not fit the LDS (or C % 8, hidden % 4, hidden > 32)"; return AERO_ERR_UNSUPPORTED; }
+    if ((((uintptr_t)d->x | (rw ? 0 : (uintptr_t)d->y)) & 15)) { *err = "dconv: unaligned rows"; return AERO_ERR_ARG; }
+    if (rw) {
+        if (!rw->rw_w || !rw->rw_bias || !rw->dst) { *err = "dconv rewrite: null pointer"; return AERO_ERR_ARG; }
+        if ((((uintptr_t)rw->rw_w | (uintptr_t)rw->rw_bias | (uintptr_t)rw->post_add | (uintptr_t)rw->dst) & 15) || ((rw->d_b | rw->d_f | rw->d_t) & 7) || rw->d_t < d->C)
+            { *err = "dconv rewrite: unaligned weights / output rows"; return AERO_ERR_ARG; }
+        if (d->R % d->F) { *err = "dconv rewrite: R is not a multiple of F"; return AERO_ERR_ARG; }
+    }
+    if (!aero_dconv_row_fits_impl(d->T, d->C, d->hidden, maxdil, rw != nullptr)) { *err = "dconv: row does not fit the LDS (or C % 8, hidden % 4, hidden > 32; with the rewrite tail C % 16)"; return AERO_ERR_UNSUPPORTED; }
     if (d->R > 0x7fffffff) { *err = "dconv: grid too large"; return AERO_ERR_ARG; }
     AeroDconvK p;
     p.d = *d;
@@ -321,17 +397,27 @@ static int aero_dconv_launch(const aero_dconv_desc* d, hipStream_t stream, const
     p.logp = aero_dconv_logp(d->C);
     p.T16 = (d->T + 15) / 16 * 16;
     p.PADR = (maxdil + 7) / 8 * 8;
-    const size_t lds = aero_dconv_lds_bytes(d->T, d->C, d->hidden, maxdil);
+    p.rw_w = rw ? rw->rw_w : nullptr;
+    p.rw_b = rw ? rw->rw_bias : nullptr;
+    p.rw_add = rw ? rw->post_add : nullptr;
+    p.out = rw ? rw->dst : nullptr;
+    p.o_b = rw ? rw->d_b : 0; p.o_f = rw ? rw->d_f : 0; p.o_t = rw ? rw->d_t : 0;
+    const size_t lds = rw ? aero_dconv_rw_lds_bytes(d->T, d->C, d->hidden, maxdil) : aero_dconv_lds_bytes(d->T, d->C, d->hidden, maxdil);
     const int nw = aero_dconv_nw(lds, d->T), nf2 = d->C / 8;
     dim3 grid((unsigned)d->R), block((unsigned)nw * 64);
-#define AERO_DCONV_GO(NF2_)                                                                                            \
+#define AERO_DCONV_GO2(NF2_, RW_)                                                                                      \
     do {                                                                                                               \
         constexpr int MF16 = NF2_ >= 12 ? 2 : 4;     /* wide rows: 16 waves x 2 fragments (T <= 512; longer rows do not fit the LDS) */ \
         if (nw == 16 && (d->T + 15) / 16 > 16 * MF16) { *err = "dconv: row too long"; return AERO_ERR_UNSUPPORTED; }    \
-        if (p.HP == 16 && nw == 8) AERO_LAUNCH_DYN((aero_dconv_row_kernel<1, NF2_, 8, 4>), grid, block, lds, stream, p);  \
-        else if (p.HP == 16) AERO_LAUNCH_DYN((aero_dconv_row_kernel<1, NF2_, 16, MF16>), grid, block, lds, stream, p);       \
-        else if (nw == 8) AERO_LAUNCH_DYN((aero_dconv_row_kernel<2, NF2_, 8, 4>), grid, block, lds, stream, p);           \
-        else AERO_LAUNCH_DYN((aero_dconv_row_kernel<2, NF2_, 16, MF16>), grid, block, lds, stream, p);                       \
+        if (p.HP == 16 && nw == 8) AERO_LAUNCH_DYN((aero_dconv_row_kernel<1, NF2_, 8, 4, RW_>), grid, block, lds, stream, p);  \
+        else if (p.HP == 16) AERO_LAUNCH_DYN((aero_dconv_row_kernel<1, NF2_, 16, MF16, RW_>), grid, block, lds, stream, p);       \
+        else if (nw == 8) AERO_LAUNCH_DYN((aero_dconv_row_kernel<2, NF2_, 8, 4, RW_>), grid, block, lds, stream, p);           \
+        else AERO_LAUNCH_DYN((aero_dconv_row_kernel<2, NF2_, 16, MF16, RW_>), grid, block, lds, stream, p);                       \
+    } while (0)
+#define AERO_DCONV_GO(NF2_)                                                                                            \
+    do {                                                                                                               \
+        if (rw) AERO_DCONV_GO2(NF2_, true);                                                                            \
+        else AERO_DCONV_GO2(NF2_, false);                                                                              \
     } while (0)
     switch (nf2) {
         case 2: AERO_DCONV_GO(2); break;
@@ -342,5 +428,6 @@ static int aero_dconv_launch(const aero_dconv_desc* d, hipStream_t stream, const
         default: AERO_DCONV_GO(16); break;
     }
 #undef AERO_DCONV_GO
+#undef AERO_DCONV_GO2
     return AERO_OK;
 }

@@ -295,9 +295,14 @@ class Ops:
         return dst
 
     def pw(self, spec, x, B, F, T, res=None, post_add=None, stats=None, count=None, gamma=None, beta=None, layer_scale=None,
-           eps=1e-5, tag='aero_pw_kernel', x1=None):
+           eps=1e-5, tag='aero_pw_kernel', x1=None, dconv=None):
         """streaming pointwise conv (aero_pw_fwd, k_pw.h): x fp16 [B,F,T,C] (channels-last view) -> [B,F,T,Mout]; optional GroupNorm
-        from per-row sums `stats` [(B*F), 2] (count = elements per row), activation of the spec, LayerScale, residual, frequency-embedding row"""
+        from per-row sums `stats` [(B*F), 2] (count = elements per row), activation of the spec, LayerScale, residual, frequency-embedding row.
+        dconv = dict(layers, act, rw): the conv (GLU, optional embedding row, nothing else) applied to the DConv branch of x, branch and conv
+        in ONE launch of the row kernel (dconv_row with `rewrite`); rw is the spec's weights as pack.dconv_rewrite_image"""
+        if dconv is not None:
+            assert spec.act == ACT_GLU and res is None and stats is None and layer_scale is None and x1 is None
+            return self.dconv_row(x, dconv['layers'], dconv['act'], F, rewrite=dconv['rw'], post_add=post_add)
         Mout = spec.M // 2 if spec.act == ACT_GLU else spec.M
         dst = torch.empty(B, F, T, Mout, dtype=torch.float16, device=x.device)
         d = _lib.PwDesc()
@@ -511,12 +516,15 @@ def _enc0(self, xn, u, g, P, conv, Fo, stride, pad, act):
 Ops.enc0 = _enc0
 
 
-def _dconv_row(self, x, layers, act, F, eps=1e-5):
-    """aero_dconv_row_fwd: every layer of a DConv branch (no BLSTM / LocalState) on x [B,F,T,C] in one launch; returns a new tensor"""
+def _dconv_row(self, x, layers, act, F, eps=1e-5, rewrite=None, post_add=None):
+    """aero_dconv_row_fwd: every layer of a DConv branch (no BLSTM / LocalState) on x [B,F,T,C] in one launch; returns a new tensor.
+    rewrite (pack.dconv_rewrite_image): aero_dconv_row_rewrite_fwd -- the encoder's rewrite conv + GLU (+ frequency embedding row
+    `post_add` [F, C]) behind the branch in the same launch; the branch's own output is not written, the result is the rewrite's [B,F,T,C]."""
     B, Fq, T, Cc = x.shape
     out = torch.empty_like(x)
-    d = _lib.DconvDesc()
-    d.x, d.y = _ptr(x), _ptr(out)
+    r = _lib.DconvRewriteDesc()
+    d = r.dconv
+    d.x, d.y = _ptr(x), (None if rewrite is not None else _ptr(out))
     d.R, d.T, d.C, d.hidden, d.depth, d.act, d.F, d.eps = B * Fq, T, Cc, layers[0]['hidden'], len(layers), act, F, eps
     flops = 0.0
     for i, L in enumerate(layers):
@@ -524,13 +532,20 @@ def _dconv_row(self, x, layers, act, F, eps=1e-5):
         l.w1, l.w2, l.consts, l.snake_a = _ptr(L['w1']), _ptr(L['w2']), _ptr(L['consts']), _ptr(L.get('snake_a'))
         l.dilation, l.norm1, l.norm2 = L['dilation'], L['norm1'], L['norm2']
         flops += 2.0 * B * Fq * T * L['hidden'] * (3 * Cc + 2 * Cc)
-    self._shape_note = f'dconv rows C={Cc} hidden={layers[0]["hidden"]} depth={len(layers)} F={Fq}'
-    self._call('aero_dconv_row_fwd', 'aero_dconv_row_kernel', flops, 2 * x.numel() * 2, C.byref(d), self.stream(x))
+    if rewrite is None:
+        self._shape_note = f'dconv rows C={Cc} hidden={layers[0]["hidden"]} depth={len(layers)} F={Fq}'
+        self._call('aero_dconv_row_fwd', 'aero_dconv_row_kernel', flops, 2 * x.numel() * 2, C.byref(d), self.stream(x))
+        return out
+    r.rw_w, r.rw_bias, r.post_add, r.dst = _ptr(rewrite['w']), _ptr(rewrite['bias']), _ptr(post_add), _ptr(out)
+    r.d_b, r.d_f, r.d_t = _strides4(out)
+    self._shape_note = f'dconv rows + rewrite C={Cc} hidden={layers[0]["hidden"]} depth={len(layers)} F={Fq}'
+    self._call('aero_dconv_row_rewrite_fwd', 'aero_dconv_row_kernel', flops + 2.0 * B * Fq * T * 2 * Cc * Cc, 2 * x.numel() * 2, C.byref(r), self.stream(x))
     return out
 
 
-def _dconv_row_fits(self, T, Cc, hidden, maxdil):
-    return bool(self.lib.cdll.aero_dconv_row_fits(T, Cc, hidden, maxdil))
+def _dconv_row_fits(self, T, Cc, hidden, maxdil, rewrite=False):
+    fn = self.lib.cdll.aero_dconv_row_rewrite_fits if rewrite else self.lib.cdll.aero_dconv_row_fits
+    return bool(fn(T, Cc, hidden, maxdil))
 
 
 Ops.dconv_row = _dconv_row
@@ -619,6 +634,7 @@ class HipEngine:
         self.split_taps = os.environ.get('AERO_TAP_SPLIT', '1') != '0'        # long thin FTB Conv1d: 3 x the blocks, partial sums summed in fixed order
         self.use_pw = os.environ.get('AERO_PW', '1') != '0'                   # streaming pointwise kernel (k_pw.h) for the DConv tails / rewrite + GLU convs
         self.fuse_dconv_row = os.environ.get('AERO_DCONV_ROW', '1') != '0'    # DConv branches without LSTM / attention: one launch, the row stays in LDS (k_dconv.h)
+        self.fuse_dconv_rewrite = os.environ.get('AERO_DCONV_ROW_REWRITE', '1') != '0'    # ... with the rewrite conv + GLU behind it as the kernel's tail pass (encoders without GroupNorm)
         self.fuse_enc0 = os.environ.get('AERO_FUSE_ENC0', '1') != '0'     # ... and fused with the layer's strided conv (k_enc0.h)
         self.fuse_tail = os.environ.get('AERO_FUSE_TAIL', '1') != '0'     # last decoder layer: the transposed conv inside the rewrite conv's epilogue (k_conv_ring.h)
         self.pitched_out = os.environ.get('AERO_PITCHED_OUT', '1') != '0' # ... its output rows at the cache-line pitch the iSTFT kernel reads (aero_istft_pitch)
@@ -726,6 +742,8 @@ class HipEngine:
                         L['rewrite_pw'] = pack.make_pw_spec(w[0, :, 0, :], sd[f'{p}.rewrite.bias'], ACT_NONE, self.lib, device)
                 elif len(df) == 1:                                 # pointwise rewrite + GLU with no norm between: the streaming kernel (k_pw.h)
                     L['rewrite_pw'] = pack.make_pw_spec(w[0, :, 0, :], sd[f'{p}.rewrite.bias'], ACT_GLU, self.lib, device)
+                    if L['rewrite_pw'] is not None and w.shape[1] == 2 * w.shape[-1]:      # ... or the tail pass of the DConv row kernel (k_dconv.h)
+                        L['rewrite_row'] = pack.dconv_rewrite_image(w[0, :, 0, :], sd[f'{p}.rewrite.bias'], device)
             P[p] = L
         for j, dec in enumerate(m.decoder):
             p = f'decoder.{j}'
@@ -947,7 +965,8 @@ class HipEngine:
         removes the per-launch Python / ctypes / runtime cost.  Inputs are copied into the graph's static buffer;
         outputs are cloned out of it (the graph's memory is reused by the next replay)."""
         key = ('graph', tuple(mix.shape), str(mix.device), want_spec, want_lr_spec,
-               self.fuse_dconv_tail, self.fuse_stats, self.collapse_first_ftb, self.fuse_lstm_proj, self.fuse_enc0, self.fuse_dconv_row, self.split_taps)
+               self.fuse_dconv_tail, self.fuse_stats, self.collapse_first_ftb, self.fuse_lstm_proj, self.fuse_enc0, self.fuse_dconv_row, self.fuse_dconv_rewrite,
+               self.split_taps)
         self._prepare(mix.device)                       # (drops the captured graphs if the weights changed)
         ent = self._tables.get(key)
         if ent is None:
@@ -1152,6 +1171,14 @@ class HipEngine:
     def _encode_rest(self, i, enc, L, y, B, Fo, T):
         ops = self.ops
         self._mark(i + 0.25)                                # (stage marks for BatchPipeline's stagger: the layer's conv is out)
+        if 'dconv' in L and self._row_rewrite_applies(enc, L, y, T):
+            # DConv branch + rewrite conv + GLU (+ frequency embedding) in ONE launch: the branch's output stays in the LDS (k_dconv.h)
+            layers = L['dconv']
+            act = {'snake': ACT_SNAKE, 'gelu': ACT_GELU}.get(enc.dconv.act_func, ACT_RELU)
+            y = ops.pw(L['rewrite_pw'], y, B, Fo, T, post_add=self.P.get('freq_emb') if i == 0 else None,
+                       dconv=dict(layers=[dict(Lr['row'], snake_a=Lr.get('snake_a')) for Lr in layers], act=act, rw=L['rewrite_row']))
+            self._mark(i + 0.75)
+            return y, Fo
         if 'dconv' in L:
             self._mark_base = i
             y = self._dconv(enc.dconv, L['dconv'], y, B, Fo, T)
@@ -1180,6 +1207,20 @@ class HipEngine:
         elif i == 0 and 'freq_emb' in self.P:
             raise NotImplementedError('frequency embedding without a rewrite conv')
         return y, Fo
+
+    def _row_rewrite_applies(self, enc, L, y, T):
+        """the fused DConv + rewrite launch: where _dconv would take the row kernel, the rewrite is pointwise with no GroupNorm before
+        its GLU, the engine is not recording for a backward pass, and the rewrite weights fit the LDS next to the row"""
+        layers = L['dconv']
+        if not (getattr(self, 'fuse_dconv_rewrite', False) and self.fuse_dconv_row and self.use_pw and not enc.norm
+                and not getattr(self, '_train', False) and L.get('rewrite_row') is not None and y.is_contiguous()
+                and all('row' in Lr for Lr in layers) and len(layers) <= _lib.DCONV_MAX_DEPTH):
+            return False
+        r0 = layers[0]['row']
+        if L['rewrite_row']['C'] != r0['C']:
+            return False
+        maxdil = max(Lr['row']['dilation'] for Lr in layers)
+        return self.ops.dconv_row_fits(T, r0['C'], r0['hidden'], maxdil) and self.ops.dconv_row_fits(T, r0['C'], r0['hidden'], maxdil, rewrite=True)
 
     def _mark(self, stage):
         if self.stage_hook is not None and not getattr(self, '_train', False):

@@ -298,3 +298,18 @@ def dconv_row_layer(w1, b1, g1, be1, w2, b2, g2, be2, scale, dilation, device):
     return dict(w1=i1.to(device=device, dtype=torch.float16).contiguous(), w2=i2.to(device=device, dtype=torch.float16).contiguous(),
                 consts=c.to(device).contiguous(), norm1=int(g1 is not None), norm2=int(g2 is not None), dilation=int(dilation),
                 C=Cc, hidden=hid)
+
+
+def dconv_rewrite_image(w, bias, device):
+    """The encoder's rewrite conv [2C, C] (+ bias [2C]) behind a DConv branch for the tail pass of aero_dconv_row_rewrite_fwd
+    (include/aero_hip.h): rows GLU-interleaved, MFMA 16x16x32 A fragments in lane order [C/8][ceil(C/32)][64 lanes][8], columns zero
+    padded to a multiple of 32.  None if C % 16."""
+    M, Cc = w.shape
+    if M != 2 * Cc or Cc % 16:
+        return None
+    ks = (Cc + 31) // 32
+    wi = torch.zeros(M, ks * 32)
+    wi[:, :Cc] = glu_interleave(w.detach().float().cpu())
+    img = wi.reshape(M // 16, 16, ks, 4, 8).permute(0, 2, 3, 1, 4).contiguous()         # [mf, ks, g, col, e]
+    b = torch.zeros(M) if bias is None else glu_interleave(bias.detach().float().cpu())
+    return dict(w=img.to(device=device, dtype=torch.float16).contiguous(), bias=b.to(device).contiguous(), C=Cc)

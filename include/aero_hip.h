@@ -384,6 +384,26 @@ typedef struct {
 int aero_dconv_row_fwd(const aero_dconv_desc* d, void* stream);
 int aero_dconv_row_fits(int T, int C, int hidden, int max_dilation);
 
+/* K14 + K9': the same DConv branch FOLLOWED BY the encoder's rewrite conv + GLU (+ frequency embedding) where no GroupNorm sits between
+ * them (modules.py:221-249, then aero.py:133, 475-480: rewrite = Conv2d(C, 2C, 1), glu(dim=1), + freq_emb row at encoder 0), as a tail pass of
+ * the row kernel on the row it still holds in the LDS: the DConv output is never written (dconv.y is ignored), only
+ *   dst[b, f, t, c] = fp16( r[c] * sigmoid(r[C + c]) + post_add[f][c] ),   r = W_rw . x'[b, f, t, :] + b_rw,   x' = the fp16 DConv output,
+ * at dst + b*d_b + f*d_f + t*d_t + c (strides in elements, multiples of 8; b = row / dconv.F, f = row % dconv.F, dconv.R a multiple of
+ * dconv.F): what aero_dconv_row_fwd followed by aero_pw_fwd (AERO_ACT_GLU, post_add) writes.
+ *   rw_w: fp16 image of W_rw [2C][C] with GLU-interleaved rows (a0, b0, a1, b1, ...) as MFMA 16x16x32 A fragments in lane order
+ *   (aero_amd/pack.py: dconv_rewrite_image): [C/8 row fragments mf][KS = ceil(C/32)][64 lanes][8], element (mf, ks, lane, e) =
+ *   W[16 mf + lane%16][32 ks + 8 (lane/16) + e], zero for columns >= C.
+ *   rw_bias fp32 [2C] in the row order of rw_w; post_add fp32 [F][C] or NULL.  All pointers 16-byte aligned.
+ * Geometry as aero_dconv_row_fwd and C % 16 == 0; the weight image takes the LDS the last layer's weights leave free:
+ * aero_dconv_row_rewrite_fits(T, C, hidden, largest dilation) == 1. */
+typedef struct {
+    aero_dconv_desc dconv;
+    const void* rw_w; const float* rw_bias; const float* post_add;
+    void* dst; int64_t d_b, d_f, d_t;
+} aero_dconv_rewrite_desc;
+int aero_dconv_row_rewrite_fwd(const aero_dconv_rewrite_desc* d, void* stream);
+int aero_dconv_row_rewrite_fits(int T, int C, int hidden, int max_dilation);
+
 /* Optimizer step of the generator (train.py:83: torch.optim.Adam(params, lr, betas=(0.9, beta2)); solver.py:602-605), fused over a
  * flat buffer: p, g, m, v fp32 [n], 16-byte aligned (parameters and gradients are views into p and g).  step >= 1 is the
  * 1-based step count of the bias corrections; every gradient is multiplied by grad_scale first (1 / world size after a summing
