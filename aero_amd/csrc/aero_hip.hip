@@ -4,7 +4,7 @@
 // the product.)
 //
 // Built by __graft_entry__.build():  hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c -DAERO_PART=k  for k = 0..9 (no 5), IN PARALLEL,
-// then one link into aero_amd/libaero_hip.so.  The library is ONE source file cut into six independently compiled parts (each
+// then one link into aero_amd/libaero_hip.so.  The library is ONE source file cut into nine independently compiled parts (each
 // kernel header belongs to exactly one part; a part holds the entry points over its kernels): as a single translation unit it took
 // four minutes to compile; now a change to one header rebuilds one part.  Without -DAERO_PART (the emulator's build) the file is the
 // whole library in one unit, as before.  EVERY device build carries `-Xclang -target-feature -Xclang -packed-fp32-ops
@@ -430,12 +430,16 @@ int aero_rescale_f16(const void* a, const float* sa, const void* b, const float*
 #endif  // part 1
 
 // ---------------------------------------------------------------------------------------------------------------
-// part 2 -- convolution family incl. the software-pipelined ring kernel   (k_conv.h k_conv_ring.h)
+// part 2 -- convolution family (k_conv.h); its software-pipelined ring kernel (k_conv_ring.h) is part 6
 #if AERO_IN(2)
 
 int aero_conv_fwd(const aero_conv_desc* d, void* stream) {
     const char* err = "";
-    int rc = aero_conv_launch(d, (hipStream_t)stream, &err);
+    AeroConvK p;
+    AeroConvPlan plan;
+    int rc = aero_conv_check(d, &err);
+    if (rc == AERO_OK) rc = aero_conv_plan(d, p, plan, &err);
+    if (rc == AERO_OK) aero_conv_issue(plan, p, (hipStream_t)stream);
     return aero_finish(rc, err);
 }
 
@@ -445,8 +449,13 @@ int aero_conv_kernel_name(const aero_conv_desc* d, char* name, int32_t cap) {
     if (!name || cap < 96) return aero_fail(AERO_ERR_ARG, "conv_kernel_name: buffer of >= 96 bytes required");
     const char* err = "";
     name[0] = 0;
-    int rc = aero_conv_launch(d, nullptr, &err, name);
-    return rc == AERO_OK ? AERO_OK : aero_fail(rc, err);
+    AeroConvK p;
+    AeroConvPlan plan;
+    int rc = aero_conv_check(d, &err);
+    if (rc == AERO_OK) rc = aero_conv_plan(d, p, plan, &err);
+    if (rc != AERO_OK) return aero_fail(rc, err);
+    aero_conv_plan_name(plan, name);
+    return AERO_OK;
 }
 
 int aero_split_finish(const float* acc, int32_t nsplit, const float* bias, int32_t act, void* dst, int64_t npos, int32_t M, void* stream) {
@@ -626,7 +635,8 @@ int aero_avgpool1d_bwd(const void* dy, void* dx, int32_t B, int32_t T, void* str
 #endif  // part 5 (compiled with part 4: the critic's weight gradients end in k_bwd.h's slab-finish kernel)
 
 // ---------------------------------------------------------------------------------------------------------------
-// part 6 -- the software-pipelined ring kernel (k_conv_ring.h), entered from part 2's aero_conv_launch through aero_conv_ring_try
+// part 6 -- the software-pipelined ring kernel (k_conv_ring.h), entered from part 2's aero_conv_plan / aero_conv_issue through
+// aero_conv_ring_plan / aero_conv_ring_issue
 #if AERO_IN(6)
 
 int aero_conv_ring_bm(int32_t M, int32_t Ktot) { return aero_conv_ring_pick_bm(M, Ktot); }

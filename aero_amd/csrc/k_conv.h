@@ -1525,6 +1525,43 @@ __global__ __launch_bounds__(256) void aero_convtr_carry_kernel(AeroConvK p, int
     }
 }
 
+// fp32 partial-sum accumulator of a tap-split conv -> fp16 activation: dst[pos][m] = act(acc[pos][m] + bias[m])
+__global__ __launch_bounds__(256) void aero_split_finish_kernel(const float* acc, int nsplit, const float* bias, int act, h16* dst, int64_t n, int M) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        float v = acc[i];
+        for (int s = 1; s < nsplit; ++s) v += acc[(int64_t)s * n + i];
+        v += bias ? bias[(int)(i % M)] : 0.f;
+        if (act == AERO_ACT_RELU) v = fmaxf(v, 0.f);
+        else if (act == AERO_ACT_GELU) v = aero_gelu(v);
+        dst[i] = (h16)v;
+    }
+}
+static int aero_split_finish_launch(const float* acc, int nsplit, const float* bias, int act, void* dst, int64_t npos, int M, hipStream_t stream, const char** err) {
+    if (!acc || !dst || npos < 1 || M < 1 || nsplit < 1) { *err = "split_finish: bad arguments"; return AERO_ERR_ARG; }
+    if (act != AERO_ACT_NONE && act != AERO_ACT_RELU && act != AERO_ACT_GELU) { *err = "split_finish: unsupported act"; return AERO_ERR_UNSUPPORTED; }
+    const int64_t n = npos * M;
+    const int64_t want = (n + 255) / 256;
+    AERO_LAUNCH(aero_split_finish_kernel, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), stream, acc, nsplit, bias, act, (h16*)dst, n, M);
+    return AERO_OK;
+}
+
+// aero_conv_fwd on the host: aero_conv_check (arguments) -> aero_conv_plan (which kernel, with which geometry; no HIP call) ->
+// aero_conv_issue (the launch).  aero_conv_kernel_name stops after the plan and prints it: tests/test_conv_dispatch.py pins that table.
+// The A/B switches of this file (README.md) are read once per process:
+struct AeroConvEnv {
+    int glds = aero_env_on(getenv("AERO_CONV_GLDS"));           // =0 selects the register-staged pipeline (A/B experiments, bisecting)
+    int mode = aero_env_int(getenv("AERO_CONV_MODE"), 0);       // =1/2 forces 32-/64-channel K-chunks in the glds pipeline (A/B); 0 = automatic
+    int wide = aero_env_int(getenv("AERO_CONV_BM256"), 2);      // 256-/192-row 8-wave tiles: =0 disables (A/B), =1 only the 256-row tile
+    int kmin192 = aero_env_int(getenv("AERO_CONV_KMIN192"), 384);   // shortest contraction the 8-wave 192-row tile takes (aero_conv_plan)
+    int skinny = aero_env_on(getenv("AERO_CONV_SKINNY")), stream = aero_env_on(getenv("AERO_CONV_STREAM"));   // the M <= 16 kernels
+    int tiny = getenv("AERO_CONV_TINY_OFF") == nullptr;
+    int carry = aero_env_on(getenv("AERO_CONVTR_CARRY"));
+    const char* qc_set = getenv("AERO_CARRY_QC");               // source rows per chunk of the carried-tap kernel (experiments); unset: by shape
+    int qc = aero_env_int(qc_set, 0);
+    int debug = getenv("AERO_CONV_DEBUG") ? 1 : 0;              // print every conv descriptor that is launched
+};
+static const AeroConvEnv& aero_conv_env() { static const AeroConvEnv env; return env; }
+
 static bool aero_conv_regular_taps(const aero_conv_desc* d, AeroConvK* p) {
     const int n = d->ntaps;
     int nT = 1;
@@ -1547,26 +1584,6 @@ static bool aero_conv_regular_taps(const aero_conv_desc* d, AeroConvK* p) {
     return true;
 }
 
-// AERO_CONV_GLDS=0 in the environment selects the register-staged pipeline (A/B experiments, bisecting)
-static int aero_conv_use_glds() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("AERO_CONV_GLDS");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v;
-}
-
-// AERO_CONV_MODE=1/2 forces 32-/64-channel K-chunks in the glds pipeline (A/B experiments); default 0 = automatic
-static int aero_conv_glds_mode() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("AERO_CONV_MODE");
-        v = e ? atoi(e) : 0;
-    }
-    return v;
-}
-
 static int aero_conv_pick_bm(int M, int Mpad) {
     const int cand[6] = {128, 96, 64, 48, 32, 16};
     int best = 128;
@@ -1584,45 +1601,7 @@ static int aero_conv_pick_bm(int M, int Mpad) {
     return best;
 }
 
-// `name` != NULL: dry run -- only report which kernel instantiation would run (profiling labels that match rocprofv3)
-#define AERO_CONV_GO_GLDS(A, B, C_)                                                                                             \
-    do {                                                                                                                        \
-        const size_t dyn = AeroGldsGeom<A, B, C_, 4>::SMEM * sizeof(h16);                                                       \
-        if (name) snprintf(name, 96, "aero_conv_glds_kernel<" #A ", " #B ", " #C_ ", %s>", d->stat_mode ? "true" : "false");    \
-        else if (d->stat_mode) AERO_LAUNCH_DYN((aero_conv_glds_kernel<A, B, C_, true>), grid, block, dyn, stream, p);           \
-        else AERO_LAUNCH_DYN((aero_conv_glds_kernel<A, B, C_, false>), grid, block, dyn, stream, p);                            \
-    } while (0)
-#define AERO_CONV_GO2(K, A, B)                                                                                 \
-    do {                                                                                                       \
-        if (name) snprintf(name, 96, #K "<" #A ", " #B ", %s>", d->stat_mode ? "true" : "false");             \
-        else if (d->stat_mode) AERO_LAUNCH((K<A, B, true>), grid, block, stream, p);                           \
-        else AERO_LAUNCH((K<A, B, false>), grid, block, stream, p);                                            \
-    } while (0)
-
-// fp32 partial-sum accumulator of a tap-split conv -> fp16 activation: dst[pos][m] = act(acc[pos][m] + bias[m])
-__global__ __launch_bounds__(256) void aero_split_finish_kernel(const float* acc, int nsplit, const float* bias, int act, h16* dst, int64_t n, int M) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        float v = acc[i];
-        for (int s = 1; s < nsplit; ++s) v += acc[(int64_t)s * n + i];
-        v += bias ? bias[(int)(i % M)] : 0.f;
-        if (act == AERO_ACT_RELU) v = fmaxf(v, 0.f);
-        else if (act == AERO_ACT_GELU) v = aero_gelu(v);
-        dst[i] = (h16)v;
-    }
-}
-static int aero_split_finish_launch(const float* acc, int nsplit, const float* bias, int act, void* dst, int64_t npos, int M, hipStream_t stream, const char** err) {
-    if (!acc || !dst || npos < 1 || M < 1 || nsplit < 1) { *err = "split_finish: bad arguments"; return AERO_ERR_ARG; }
-    if (act != AERO_ACT_NONE && act != AERO_ACT_RELU && act != AERO_ACT_GELU) { *err = "split_finish: unsupported act"; return AERO_ERR_UNSUPPORTED; }
-    const int64_t n = npos * M;
-    const int64_t want = (n + 255) / 256;
-    AERO_LAUNCH(aero_split_finish_kernel, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), stream, acc, nsplit, bias, act, (h16*)dst, n, M);
-    return AERO_OK;
-}
-
-// k_conv_ring.h: the software-pipelined 8-wave kernel for the wide contractions; returns true if it took the launch
-AERO_XPART bool aero_conv_ring_try(const aero_conv_desc* d, AeroConvK& p, hipStream_t stream, char* name);
-
-static int aero_conv_launch(const aero_conv_desc* d, hipStream_t stream, const char** err, char* name = nullptr) {
+static int aero_conv_check(const aero_conv_desc* d, const char** err) {
     if (!d || !d->weight || (!d->dst && d->stat_mode != 2 && d->tap_split <= 1 && !d->tail_w)) { *err = "conv: null weight/dst"; return AERO_ERR_ARG; }
     if (d->tail_w) {                                            // fused transposed-conv tail (aero_hip.h): only the 192-row ring tile carries it
         if (!d->tail_lo || !d->tail_hi || ((uintptr_t)d->tail_w & 15) || ((uintptr_t)d->tail_lo & 15) || ((uintptr_t)d->tail_hi & 15)) { *err = "conv: fused tail needs 16-byte aligned tail_w / tail_lo / tail_hi"; return AERO_ERR_ARG; }
@@ -1654,28 +1633,40 @@ static int aero_conv_launch(const aero_conv_desc* d, hipStream_t stream, const c
             d->dst_f32 || d->stat_mode || d->res || d->post_add || d->batch_scale || d->act == AERO_ACT_GLU || d->dst_f_off != 0 ||
             d->dst_F != d->Fout) { *err = "conv: row scatter needs a plain fp16 conv with scatter_M % 8 == 0"; return AERO_ERR_UNSUPPORTED; }
     }
-    AeroConvK p;
+    return AERO_OK;
+}
+
+// the 4-wave tiles of the glds and the generic kernel, BM = 16 * MF * WM rows: X(MF, WM, KC)
+#define AERO_CONV_TILES(X, KC) X(4, 2, KC) X(3, 2, KC) X(4, 1, KC) X(3, 1, KC) X(2, 1, KC) X(1, 1, KC)
+
+// k_conv_ring.h: the software-pipelined kernel for the wide contractions; _plan returns false if the ring does not take the descriptor
+AERO_XPART bool aero_conv_ring_plan(const aero_conv_desc* d, AeroConvK& p, AeroConvPlan& pl);
+AERO_XPART void aero_conv_ring_issue(const AeroConvPlan& pl, const AeroConvK& p, hipStream_t stream);
+
+// `d` has passed aero_conv_check.  To add a kernel family: a branch here, a case in aero_conv_issue and in aero_conv_plan_name, and the
+// entries of tests/golden/conv_dispatch.json it is meant to move.
+static int aero_conv_plan(const aero_conv_desc* d, AeroConvK& p, AeroConvPlan& pl, const char** err) {
+    const AeroConvEnv& env = aero_conv_env();
     p.d = *d;
     p.tsplit = 1;
     p.Cp = (d->C0 + d->C1 + 31) / 32 * 32;
     p.cpt = p.Cp / 32;
     p.Ktot = d->ntaps * p.Cp;
     p.Mpad = (d->M + 127) / 128 * 128;
-    const int bm = aero_conv_pick_bm(d->M, p.Mpad);
-    p.ntt = (d->T + 127) / 128;
-    p.nmt = (d->M + bm - 1) / bm;
-    auto al8 = [](int64_t v) { return (v & 7) == 0; };
-    int vin = (d->C0 % 8 == 0) && (d->C1 % 8 == 0);
-    if (d->src0) vin = vin && al8(d->s0_b) && al8(d->s0_f) && al8(d->s0_t) && (((uintptr_t)d->src0 & 15) == 0);
-    if (d->src1) vin = vin && al8(d->s1_b) && al8(d->s1_f) && al8(d->s1_t) && (((uintptr_t)d->src1 & 15) == 0);
-    p.vec_in = vin;
-    auto al4 = [](int64_t v) { return (v & 3) == 0; };
-    int v4 = (d->C0 % 4 == 0) && (d->C1 % 4 == 0);
-    if (d->src0) v4 = v4 && al4(d->s0_b) && al4(d->s0_f) && al4(d->s0_t) && (((uintptr_t)d->src0 & 7) == 0);
-    if (d->src1) v4 = v4 && al4(d->s1_b) && al4(d->s1_f) && al4(d->s1_t) && (((uintptr_t)d->src1 & 7) == 0);
-    p.vec4 = v4 && !vin;
-    p.glds = aero_conv_use_glds();
+    const int bm = aero_conv_pick_bm(d->M, p.Mpad);             // the 4-wave tiles: bm rows x 128 time steps
+    const int ntt = (d->T + 127) / 128, nmt = (d->M + bm - 1) / bm;
+    p.ntt = p.nmt = 0;                                          // (each family below writes its own meaning of the two)
+    auto fits = [&](int w) {                                    // the sources can be read in aligned pieces of w channels
+        bool ok = (d->C0 % w == 0) && (d->C1 % w == 0);
+        if (d->src0) ok = ok && d->s0_b % w == 0 && d->s0_f % w == 0 && d->s0_t % w == 0 && ((uintptr_t)d->src0 % (2 * w)) == 0;
+        if (d->src1) ok = ok && d->s1_b % w == 0 && d->s1_f % w == 0 && d->s1_t % w == 0 && ((uintptr_t)d->src1 % (2 * w)) == 0;
+        return ok;
+    };
+    p.vec_in = fits(8);
+    p.vec4 = fits(4) && !p.vec_in;
+    p.glds = env.glds;
     p.nT = 1; p.f_lo = p.f_step = p.t_lo = p.t_step = 0;
+    const bool regular = aero_conv_regular_taps(d, &p);         // (fills the five if the tap grid is regular: the stream and glds kernels read them)
     const int Mout = d->act == AERO_ACT_GLU ? d->M / 2 : d->M;
     const int nout = d->act == AERO_ACT_GLU ? 2 : 4;
     const int esz = d->dst_f32 ? 4 : 2;
@@ -1688,177 +1679,163 @@ static int aero_conv_launch(const aero_conv_desc* d, hipStream_t stream, const c
     if (d->stat_mode == 2) p.staged = 0;
     if ((d->stat_mode == 1 || d->stat_mode == 3) && !p.staged) { *err = "conv: statistics modes need an fp16 destination with 8-channel aligned rows"; return AERO_ERR_UNSUPPORTED; }
     if (d->stat_mode && (d->batch_scale || d->post_add || d->scatter_M)) { *err = "conv: statistics modes do not combine with per-item affine / frequency embedding / row scatter"; return AERO_ERR_UNSUPPORTED; }
-    const long nwg = (long)d->B * d->Fout * p.ntt * p.nmt;
+    const long nwg = (long)d->B * d->Fout * ntt * nmt;
     if (nwg <= 0 || nwg > 0x7fffffffL) { *err = "conv: grid too large"; return AERO_ERR_ARG; }
-    dim3 grid((unsigned)nwg), block(256);
-    static int dbg = -1;
-    if (dbg < 0) dbg = getenv("AERO_CONV_DEBUG") ? 1 : 0;
-    if (dbg && !name)
-        fprintf(stderr, "[aero_conv] M=%d C0=%d C1=%d ntaps=%d B=%d Fin=%d Fout=%d T=%d tr=%d fs=%d act=%d vec_in=%d f32=%d res=%d post=%d s0=%d\n",
-                d->M, d->C0, d->C1, d->ntaps, d->B, d->Fin, d->Fout, d->T, d->transposed, d->fstride, d->act, p.vec_in, d->dst_f32,
-                d->res != nullptr, d->post_add != nullptr, d->src0 != nullptr);
+    pl = AeroConvPlan{}; pl.block = 256; pl.stats = d->stat_mode != 0;
     // few channels in, few out, frequency-major destination: the transposing pointwise kernel
     if (!d->scatter_M && d->ntaps == 1 && d->df[0] == 0 && d->dt[0] == 0 && !d->transposed && d->fstride == 1 && d->C1 == 0 && d->src0 && d->C0 <= 8 &&
         d->M <= 8 && d->act != AERO_ACT_GLU && !d->res && !d->post_add && !d->batch_scale && !d->stat_mode && !d->dst_f32 &&
-        d->d_f == d->M && d->d_t == (int64_t)d->Fout * d->M && d->dst_f_off == 0 && d->dst_F == d->Fout && d->Fin == d->Fout &&
-        getenv("AERO_CONV_TINY_OFF") == nullptr) {
+        d->d_f == d->M && d->d_t == (int64_t)d->Fout * d->M && d->dst_f_off == 0 && d->dst_F == d->Fout && d->Fin == d->Fout && env.tiny) {
         p.ntt = (d->T + AERO_TINY_TT - 1) / AERO_TINY_TT;
-        p.nmt = (d->Fout + AERO_TINY_TF - 1) / AERO_TINY_TF;
+        p.nmt = (d->Fout + AERO_TINY_TF - 1) / AERO_TINY_TF;      // frequency tiles
         const long nb = (long)d->B * p.nmt * p.ntt;
         if (nb > 0x7fffffffL) { *err = "conv: grid too large"; return AERO_ERR_ARG; }
-        if (name) snprintf(name, 96, "aero_conv_tiny_kernel");
-        else AERO_LAUNCH(aero_conv_tiny_kernel, dim3((unsigned)nb), block, stream, p);
+        pl.tile(AERO_CONV_TINY);
+        pl.grid = (unsigned)nb;
         return AERO_OK;
     }
-    static int skinny = -1;
-    if (skinny < 0) { const char* e = getenv("AERO_CONV_SKINNY"); skinny = (e && e[0] == '0') ? 0 : 1; }
+    const int nk = d->ntaps * p.cpt;                              // worst-case K-chunks per 64-step segment
+    const int nseg = (d->T + 63) / 64;
+    const int stack = d->transposed ? d->fstride : 1;
     // lean streaming form: one aligned source, regular taps, <= 6 chunks per segment, dense destination
-    static int stream_on = -1;
-    if (stream_on < 0) { const char* e = getenv("AERO_CONV_STREAM"); stream_on = (e && e[0] == '0') ? 0 : 1; }
-    if (skinny && stream_on && !d->scatter_M && p.vec_in && d->src0 && d->C1 == 0 && d->act != AERO_ACT_GLU && !d->res && !d->post_add && !d->stat_mode) {
-        const int stack = d->transposed ? d->fstride : 1;
-        const int nk = d->ntaps * p.cpt;
+    if (env.skinny && env.stream && !d->scatter_M && p.vec_in && d->src0 && d->C1 == 0 && d->act != AERO_ACT_GLU && !d->res && !d->post_add && !d->stat_mode) {
         const bool dense = d->d_t == d->M && (((uintptr_t)d->dst & 3) == 0);
         const bool small = (int64_t)d->B * d->s0_b < 0x7fffffffLL && (int64_t)(d->T + 64) * d->s0_t + p.Cp < 0x7fffffffLL &&
                            (int64_t)d->B * d->Fout * ((d->T + 63) / 64) < 0x7fffffffLL;
-        if (stack * d->M <= 16 && nk <= AERO_STREAM_SLOTS && dense && small && p.Ktot + 8 <= AERO_SKINNY_WMAX &&
-            aero_conv_regular_taps(d, &p) && (!d->transposed || (p.f_step == -1 && p.f_lo == 0))) {
+        if (stack * d->M <= 16 && nk <= AERO_STREAM_SLOTS && dense && small && p.Ktot + 8 <= AERO_SKINNY_WMAX && regular &&
+            (!d->transposed || (p.f_step == -1 && p.f_lo == 0))) {
+            const int NR = (d->Fout + stack - 1) / stack;       // source rows
             // last decoder ConvTranspose: carried-tap form, every source row read once
-            static int carry_on = -1;
-            if (carry_on < 0) { const char* e = getenv("AERO_CONVTR_CARRY"); carry_on = (e && e[0] == '0') ? 0 : 1; }
-            if (carry_on && d->transposed && d->ntaps == 2 && p.nT == 1 && p.t_lo == 0 && d->fstride * d->M <= 8 && d->C0 % 32 == 0 && d->C0 <= 128 &&
+            if (env.carry && d->transposed && d->ntaps == 2 && p.nT == 1 && p.t_lo == 0 && d->fstride * d->M <= 8 && d->C0 % 32 == 0 && d->C0 <= 128 &&
                 d->C0 == p.Cp && (d->s0_t % 8) == 0 && (d->s0_f % 8) == 0 && (d->s0_b % 8) == 0 && (((uintptr_t)d->src0 & 15) == 0) &&
                 (d->M != 2 || ((d->d_b % 2) == 0 && (d->d_f % 2) == 0 && (((uintptr_t)d->dst & 7) == 0)))) {
-                const int NRq = (d->Fout + d->fstride - 1) / d->fstride;
-                const int nsegq = (d->T + 63) / 64;
                 // rows per wave: as few chunks as give every CU a block (each chunk re-reads one row to start its carry).  Measured at
                 // B = 64 (8 segments, 65 row groups): 2 chunks 104 us, 3: 108-114, 5: 121, 9: 107-120 -- more resident waves buy nothing,
                 // the kernel sits at ~4.4 TB/s either way, and partial last rounds cost
-                int nchq = (int)((256L * 4 + (long)d->B * nsegq - 1) / ((long)d->B * nsegq));
-                if (nchq > NRq / 4) nchq = NRq / 4;
-                if (nchq < 1) nchq = 1;
-                int QC = (NRq + nchq - 1) / nchq;
-                { const char* e = getenv("AERO_CARRY_QC"); if (e) QC = atoi(e); }
-                const long nitq = (long)d->B * nsegq * ((NRq + QC - 1) / QC);
-                const int ncc = d->C0 / 32;
-                if (name) snprintf(name, 96, "aero_convtr_carry_kernel<%d>", ncc);
-                else if (ncc == 1) AERO_LAUNCH(aero_convtr_carry_kernel<1>, dim3((unsigned)((nitq + 3) / 4)), block, stream, p, QC);
-                else if (ncc == 2) AERO_LAUNCH(aero_convtr_carry_kernel<2>, dim3((unsigned)((nitq + 3) / 4)), block, stream, p, QC);
-                else if (ncc == 3) AERO_LAUNCH(aero_convtr_carry_kernel<3>, dim3((unsigned)((nitq + 3) / 4)), block, stream, p, QC);
-                else AERO_LAUNCH(aero_convtr_carry_kernel<4>, dim3((unsigned)((nitq + 3) / 4)), block, stream, p, QC);
+                int nch = (int)((256L * 4 + (long)d->B * nseg - 1) / ((long)d->B * nseg));
+                if (nch > NR / 4) nch = NR / 4;
+                if (nch < 1) nch = 1;
+                pl.QC = env.qc_set ? env.qc : (NR + nch - 1) / nch;
+                const long nitems = (long)d->B * nseg * ((NR + pl.QC - 1) / pl.QC);
+                pl.tile(AERO_CONV_CARRY, d->C0 / 32);
+                pl.grid = (unsigned)((nitems + 3) / 4);
                 return AERO_OK;
             }
             p.nmt = AERO_STREAM_SLOTS / nk;                       // segments per wave item
-            const int nseg = (d->T + 63) / 64;
-            const int NR = d->transposed ? (d->Fout + d->fstride - 1) / d->fstride : d->Fout;
-            const long nitems = (long)d->B * NR * ((nseg + p.nmt - 1) / p.nmt);
-            const long want = (nitems + 3) / 4;
-            const long nb = want < 256 * 2 ? want : 256 * 2;
-            if (name) snprintf(name, 96, "aero_conv_stream_kernel");
-            else AERO_LAUNCH(aero_conv_stream_kernel, dim3((unsigned)nb), block, stream, p);
+            const long want = ((long)d->B * NR * ((nseg + p.nmt - 1) / p.nmt) + 3) / 4;
+            pl.tile(AERO_CONV_STREAM);
+            pl.grid = (unsigned)(want < 256 * 2 ? want : 256 * 2);
             return AERO_OK;
         }
-        p.nT = 1; p.f_lo = p.f_step = p.t_lo = p.t_step = 0;
     }
-    if (skinny && !d->scatter_M && d->M <= 16 && (d->transposed ? d->fstride : 1) * (p.Ktot + 8) <= AERO_SKINNY_WMAX && d->act != AERO_ACT_GLU &&
+    if (env.skinny && !d->scatter_M && d->M <= 16 && stack * (p.Ktot + 8) <= AERO_SKINNY_WMAX && d->act != AERO_ACT_GLU &&
         !d->res && !d->post_add && !d->stat_mode) {
-        const int nkmax = d->ntaps * p.cpt;                    // worst-case K-chunks per 64-step segment
-        p.nmt = nkmax >= AERO_SKINNY_SLOTS ? 1 : AERO_SKINNY_SLOTS / nkmax;      // segments per wave item
-        const int nseg = (d->T + 63) / 64;
-        const long nitems = (long)d->B * d->Fout * ((nseg + p.nmt - 1) / p.nmt);
-        const long want = (nitems + 3) / 4;
-        const long nb = want < 256 * 2 ? want : 256 * 2;      // persistent: 2 blocks (8 waves x 24 KiB of loads in flight) per CU
+        p.nmt = nk >= AERO_SKINNY_SLOTS ? 1 : AERO_SKINNY_SLOTS / nk;            // segments per wave item
+        const long want = ((long)d->B * d->Fout * ((nseg + p.nmt - 1) / p.nmt) + 3) / 4;
         int vw = 8;                                             // widest load piece the layout allows
-        auto fits = [&](int w) {
-            bool ok = (d->C0 % w == 0) && (d->C1 % w == 0);
-            if (d->src0) ok = ok && d->s0_b % w == 0 && d->s0_f % w == 0 && d->s0_t % w == 0 && ((uintptr_t)d->src0 % (2 * w)) == 0;
-            if (d->src1) ok = ok && d->s1_b % w == 0 && d->s1_f % w == 0 && d->s1_t % w == 0 && ((uintptr_t)d->src1 % (2 * w)) == 0;
-            return ok;
-        };
         while (vw > 1 && !fits(vw)) vw >>= 1;
-        if (name) snprintf(name, 96, "aero_conv_skinny_kernel<%d>", vw);
-        else if (vw == 8) AERO_LAUNCH(aero_conv_skinny_kernel<8>, dim3((unsigned)nb), block, stream, p);
-        else if (vw == 4) AERO_LAUNCH(aero_conv_skinny_kernel<4>, dim3((unsigned)nb), block, stream, p);
-        else if (vw == 2) AERO_LAUNCH(aero_conv_skinny_kernel<2>, dim3((unsigned)nb), block, stream, p);
-        else AERO_LAUNCH(aero_conv_skinny_kernel<1>, dim3((unsigned)nb), block, stream, p);
+        pl.tile(AERO_CONV_SKINNY, vw);
+        pl.grid = (unsigned)(want < 256 * 2 ? want : 256 * 2);  // persistent: 2 blocks (8 waves x 24 KiB of loads in flight) per CU
         return AERO_OK;
     }
     if (d->scatter_M && !(p.staged && p.vec_in && p.glds)) { *err = "conv: row scatter needs aligned fp16 operands (direct-to-LDS pipeline)"; return AERO_ERR_UNSUPPORTED; }
-    if (p.vec_in && p.glds && aero_conv_regular_taps(d, &p)) {
-        // 64-channel chunks pay off only for the big compute-bound contractions (measured: +5 % on the decoder 3x3
-        // convs, -2 % on the whole model if used everywhere because two 64-KiB stages halve the blocks per CU)
-        const int mode = aero_conv_glds_mode();               // 0 auto, 1 = KC 32, 2 = KC 64 where legal
-        const bool k64_ok = (p.Cp % 64 == 0);
-        // ... and for the long, thin contractions that cannot fill the chip (FTB Conv1d over time: 250 blocks x 360 chunks, one
-        // block per CU, each chunk a full copy -> barrier -> MFMA round trip): half as many, twice as long chunks (185 -> 150 us)
-        const bool thin = p.Ktot >= 2048 && (long)d->B * d->Fout * p.ntt * ((d->M + bm - 1) / bm) <= 512;
-        const bool k64 = mode == 2 ? k64_ok : (mode == 1 ? false : (k64_ok && ((bm >= 96 && p.Ktot >= 1024) || thin)));
-        // 256-/192-row tiles (8 waves) for the wide compute-bound contractions; AERO_CONV_BM256=0 disables (A/B),
-        // =1 only the 256-row tile.  KC 32 here: two 48-KiB blocks (16 waves) per CU measured 937 TF/s on the first
-        // decoder layer vs 872 with one 96-KiB KC-64 block and 860 for the 128-row KC-64 tile.
+    const int wm = bm >= 96 ? 2 : 1, mf = bm / (16 * wm);       // bm = 16 * MF * WM
+    if (p.vec_in && p.glds && regular) {
         if (d->tap_split > 1) {                                 // (4-wave tiles only: the launch is block-starved by construction)
             if (p.nT % d->tap_split) { *err = "conv: tap split must divide the time taps"; return AERO_ERR_UNSUPPORTED; }
             p.tsplit = d->tap_split;
-            grid = dim3(grid.x * (unsigned)p.tsplit);
         }
-        if (p.tsplit == 1 && aero_conv_ring_try(d, p, stream, name)) return AERO_OK;
+        if (p.tsplit == 1 && aero_conv_ring_plan(d, p, pl)) return AERO_OK;
         if (d->tail_w) { *err = "conv: fused tail needs the 192-row software-pipelined tile (3x3 taps, tiled weight image, K >= 768)"; return AERO_ERR_UNSUPPORTED; }
-        static int wide = -1;
-        if (wide < 0) { const char* e = getenv("AERO_CONV_BM256"); wide = e ? atoi(e) : 2; }
-        // shortest contraction the 8-wave 192-row tile takes (AERO_CONV_KMIN192, A/B; 768 until round 4): the two-source 1x1 conv of the
-        // third encoder's FTB (K = 384) 89 -> 78 us, the second decoder's transposed conv (K = 384) unchanged
-        static int kmin192 = -1;
-        if (kmin192 < 0) { const char* e = getenv("AERO_CONV_KMIN192"); kmin192 = e ? atoi(e) : 384; }
-        const int wbm = p.tsplit > 1 ? 0 : (wide >= 1 && d->M % 256 == 0 && p.Ktot >= 1024) ? 256
-                        : (wide >= 2 && d->M % 192 == 0 && p.Ktot >= kmin192) ? 192 : 0;
+        // 256-/192-row tiles (8 waves) for the wide compute-bound contractions (AERO_CONV_BM256).  KC 32 here: two 48-KiB blocks
+        // (16 waves) per CU measured 937 TF/s on the first decoder layer vs 872 with one 96-KiB KC-64 block and 860 for the 128-row
+        // KC-64 tile.  Shortest contraction the 192-row tile takes: 384 (AERO_CONV_KMIN192, A/B; 768 until round 4) -- the two-source
+        // 1x1 conv of the third encoder's FTB (K = 384) 89 -> 78 us, the second decoder's transposed conv (K = 384) unchanged
+        const int wbm = p.tsplit > 1 ? 0 : (env.wide >= 1 && d->M % 256 == 0 && p.Ktot >= 1024) ? 256
+                        : (env.wide >= 2 && d->M % 192 == 0 && p.Ktot >= env.kmin192) ? 192 : 0;
         if (wbm) {
-            p.nmt = d->M / wbm;
-            grid = dim3((unsigned)((long)d->B * d->Fout * p.ntt * p.nmt));
-            block = dim3(512);
-            const bool st = d->stat_mode != 0;
-            if (name) snprintf(name, 96, "aero_conv_glds8_kernel<%d, 32, %s>", wbm / 64, st ? "true" : "false");
-            else if (wbm == 256) {
-                const size_t dyn = AeroGldsGeom<4, 4, 32, 8>::SMEM * sizeof(h16);
-                if (st) AERO_LAUNCH_DYN((aero_conv_glds8_kernel<4, 32, true>), grid, block, dyn, stream, p);
-                else AERO_LAUNCH_DYN((aero_conv_glds8_kernel<4, 32, false>), grid, block, dyn, stream, p);
-            } else {
-                const size_t dyn = AeroGldsGeom<3, 4, 32, 8>::SMEM * sizeof(h16);
-                if (st) AERO_LAUNCH_DYN((aero_conv_glds8_kernel<3, 32, true>), grid, block, dyn, stream, p);
-                else AERO_LAUNCH_DYN((aero_conv_glds8_kernel<3, 32, false>), grid, block, dyn, stream, p);
-            }
+            p.ntt = ntt; p.nmt = d->M / wbm;
+            pl.tile(AERO_CONV_GLDS8, wbm / 64);
+            pl.grid = (unsigned)((long)d->B * d->Fout * p.ntt * p.nmt);
+            pl.block = 512;
+            pl.lds = (wbm == 256 ? AeroGldsGeom<4, 4, 32, 8>::SMEM : AeroGldsGeom<3, 4, 32, 8>::SMEM) * sizeof(h16);
             return AERO_OK;
         }
-        if (k64) {
-            switch (bm) {
-                case 128: AERO_CONV_GO_GLDS(4, 2, 64); break;
-                case 96: AERO_CONV_GO_GLDS(3, 2, 64); break;
-                case 64: AERO_CONV_GO_GLDS(4, 1, 64); break;
-                case 48: AERO_CONV_GO_GLDS(3, 1, 64); break;
-                case 32: AERO_CONV_GO_GLDS(2, 1, 64); break;
-                default: AERO_CONV_GO_GLDS(1, 1, 64); break;
-            }
-        } else {
-            switch (bm) {
-                case 128: AERO_CONV_GO_GLDS(4, 2, 32); break;
-                case 96: AERO_CONV_GO_GLDS(3, 2, 32); break;
-                case 64: AERO_CONV_GO_GLDS(4, 1, 32); break;
-                case 48: AERO_CONV_GO_GLDS(3, 1, 32); break;
-                case 32: AERO_CONV_GO_GLDS(2, 1, 32); break;
-                default: AERO_CONV_GO_GLDS(1, 1, 32); break;
-            }
-        }
-        return AERO_OK;
+        // 64-channel chunks pay off only for the big compute-bound contractions (measured: +5 % on the decoder 3x3
+        // convs, -2 % on the whole model if used everywhere because two 64-KiB stages halve the blocks per CU)
+        const bool k64_ok = (p.Cp % 64 == 0);
+        // ... and for the long, thin contractions that cannot fill the chip (FTB Conv1d over time: 250 blocks x 360 chunks, one
+        // block per CU, each chunk a full copy -> barrier -> MFMA round trip): half as many, twice as long chunks (185 -> 150 us)
+        const bool thin = p.Ktot >= 2048 && nwg <= 512;
+        const bool k64 = env.mode == 2 ? k64_ok : (env.mode == 1 ? false : (k64_ok && ((bm >= 96 && p.Ktot >= 1024) || thin)));
+        pl.tile(AERO_CONV_GLDS, mf, wm, k64 ? 64 : 32);
+#define AERO_X(A, B, KC) if (pl.is(A, B, KC)) pl.lds = AeroGldsGeom<A, B, KC, 4>::SMEM * sizeof(h16);
+        AERO_CONV_TILES(AERO_X, 64) AERO_CONV_TILES(AERO_X, 32)
+#undef AERO_X
+    } else {
+        if (d->scatter_M) { *err = "conv: row scatter needs a regular tap grid"; return AERO_ERR_UNSUPPORTED; }
+        if (d->tap_split > 1) { *err = "conv: tap split needs aligned fp16 operands on a regular tap grid"; return AERO_ERR_UNSUPPORTED; }
+        if (d->tail_w) { *err = "conv: fused tail needs aligned fp16 operands on a regular tap grid"; return AERO_ERR_UNSUPPORTED; }
+        pl.tile(AERO_CONV_GENERIC, mf, wm);
     }
-    if (d->scatter_M) { *err = "conv: row scatter needs a regular tap grid"; return AERO_ERR_UNSUPPORTED; }
-    if (d->tap_split > 1) { *err = "conv: tap split needs aligned fp16 operands on a regular tap grid"; return AERO_ERR_UNSUPPORTED; }
-    if (d->tail_w) { *err = "conv: fused tail needs aligned fp16 operands on a regular tap grid"; return AERO_ERR_UNSUPPORTED; }
-    switch (bm) {
-        case 128: AERO_CONV_GO2(aero_conv_kernel, 4, 2); break;
-        case 96: AERO_CONV_GO2(aero_conv_kernel, 3, 2); break;
-        case 64: AERO_CONV_GO2(aero_conv_kernel, 4, 1); break;
-        case 48: AERO_CONV_GO2(aero_conv_kernel, 3, 1); break;
-        case 32: AERO_CONV_GO2(aero_conv_kernel, 2, 1); break;
-        default: AERO_CONV_GO2(aero_conv_kernel, 1, 1); break;
-    }
+    p.ntt = ntt; p.nmt = nmt;
+    pl.grid = (unsigned)nwg * (unsigned)p.tsplit;
     return AERO_OK;
+}
+
+// the kernel instantiation as rocprofv3 prints it (profiling labels); buf: >= 96 bytes
+static void aero_conv_plan_name(const AeroConvPlan& pl, char* buf) {
+    const int* t = pl.t; const char* st = pl.stats ? "true" : "false";
+    switch (pl.family) {
+        case AERO_CONV_TINY: snprintf(buf, 96, "aero_conv_tiny_kernel"); break;
+        case AERO_CONV_CARRY: snprintf(buf, 96, "aero_convtr_carry_kernel<%d>", t[0]); break;
+        case AERO_CONV_STREAM: snprintf(buf, 96, "aero_conv_stream_kernel"); break;
+        case AERO_CONV_SKINNY: snprintf(buf, 96, "aero_conv_skinny_kernel<%d>", t[0]); break;
+        case AERO_CONV_RING: snprintf(buf, 96, "aero_conv_ring_kernel<%d, %d, %d, %d, 0>", t[0], t[1], t[2], t[3]); break;
+        case AERO_CONV_GLDS8: snprintf(buf, 96, "aero_conv_glds8_kernel<%d, 32, %s>", t[0], st); break;
+        case AERO_CONV_GLDS: snprintf(buf, 96, "aero_conv_glds_kernel<%d, %d, %d, %s>", t[0], t[1], t[2], st); break;
+        case AERO_CONV_GENERIC: snprintf(buf, 96, "aero_conv_kernel<%d, %d, %s>", t[0], t[1], st); break;
+    }
+}
+
+// One AERO_LAUNCH* call site per instantiation, the kernel named as a token: AERO_LAUNCH_DYN keeps its LDS high-water mark per call
+// site, and the emulator's launch macros print the token (aero_last_kernel_name).
+#define AERO_CONV_GO(K, ...) do { if (pl.stats) AERO_LAUNCH_DYN((K<__VA_ARGS__, true>), grid, block, pl.lds, stream, p); \
+                                  else AERO_LAUNCH_DYN((K<__VA_ARGS__, false>), grid, block, pl.lds, stream, p); } while (0)
+static void aero_conv_issue(const AeroConvPlan& pl, const AeroConvK& p, hipStream_t stream) {
+    const aero_conv_desc* d = &p.d;
+    if (aero_conv_env().debug)
+        fprintf(stderr, "[aero_conv] M=%d C0=%d C1=%d ntaps=%d B=%d Fin=%d Fout=%d T=%d tr=%d fs=%d act=%d vec_in=%d f32=%d res=%d post=%d s0=%d\n",
+                d->M, d->C0, d->C1, d->ntaps, d->B, d->Fin, d->Fout, d->T, d->transposed, d->fstride, d->act, p.vec_in, d->dst_f32,
+                d->res != nullptr, d->post_add != nullptr, d->src0 != nullptr);
+    const dim3 grid(pl.grid), block(pl.block);
+    switch (pl.family) {
+        case AERO_CONV_TINY: AERO_LAUNCH(aero_conv_tiny_kernel, grid, block, stream, p); break;
+        case AERO_CONV_CARRY:
+#define AERO_X(NCH) if (pl.is(NCH)) AERO_LAUNCH(aero_convtr_carry_kernel<NCH>, grid, block, stream, p, pl.QC);
+            AERO_X(1) AERO_X(2) AERO_X(3) AERO_X(4)
+#undef AERO_X
+            break;
+        case AERO_CONV_STREAM: AERO_LAUNCH(aero_conv_stream_kernel, grid, block, stream, p); break;
+        case AERO_CONV_SKINNY:
+#define AERO_X(VW) if (pl.is(VW)) AERO_LAUNCH(aero_conv_skinny_kernel<VW>, grid, block, stream, p);
+            AERO_X(8) AERO_X(4) AERO_X(2) AERO_X(1)
+#undef AERO_X
+            break;
+        case AERO_CONV_RING: aero_conv_ring_issue(pl, p, stream); break;
+        case AERO_CONV_GLDS8:
+            if (pl.is(4)) AERO_CONV_GO(aero_conv_glds8_kernel, 4, 32);
+            else AERO_CONV_GO(aero_conv_glds8_kernel, 3, 32);
+            break;
+        case AERO_CONV_GLDS:
+#define AERO_X(A, B, KC) if (pl.is(A, B, KC)) AERO_CONV_GO(aero_conv_glds_kernel, A, B, KC);
+            AERO_CONV_TILES(AERO_X, 64) AERO_CONV_TILES(AERO_X, 32)
+#undef AERO_X
+            break;
+        case AERO_CONV_GENERIC:
+#define AERO_X(A, B, KC) if (pl.is(A, B)) AERO_CONV_GO(aero_conv_kernel, A, B);
+            AERO_CONV_TILES(AERO_X, 0)
+#undef AERO_X
+            break;
+    }
 }

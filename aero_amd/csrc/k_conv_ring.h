@@ -597,78 +597,78 @@ __global__ __launch_bounds__(WM * WN * 64, 2) void aero_conv_ring_kernel(AeroCon
     }
 }
 
-// AERO_CONV_RING=0 keeps every conv on the k_conv.h kernels (A/B experiments, bisecting); 1 = only the 256-row tile
-static int aero_conv_ring_mode() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("AERO_CONV_RING");
-        v = e ? atoi(e) : 2;
-    }
-    return v;
-}
+// The A/B switches of this file (README.md), read once per process
+struct AeroRingEnv {
+    int mode = aero_env_int(getenv("AERO_CONV_RING"), 2);       // =0 keeps every conv on the k_conv.h kernels (A/B, bisecting); 1 = only the 256-row tile
+    int kmin256 = aero_env_int(getenv("AERO_RING_KMIN256"), 384);   // shortest contraction the 256-row tile takes (aero_conv_ring_pick_bm)
+    int tile192 = aero_env_on(getenv("AERO_RING_TILE192"));     // =0: 128 / 64-row x 512-step tiles instead of the 192 x 256 one (A/B)
+    int half = aero_env_int(getenv("AERO_RING_HALF"), 1);       // the 96-row four-wave tile: 0 = off, 1 = for M = 96, 2 = also the 192 / 384-row decoder convs
+    int narrow256 = aero_env_int(getenv("AERO_RING_256X128"), 2);   // =0 / 1 forces the wide / narrow 256-row tile (A/B); 2 = by T
+    int narrow192 = aero_env_int(getenv("AERO_RING_192X128"), 1);   // =0 restores the 8-wave 192 x 256 tile
+};
+static const AeroRingEnv& aero_ring_env() { static const AeroRingEnv env; return env; }
 
 // tile height by shape (also exported: the caller prepares `weight_tiled` for it)
 static int aero_conv_ring_pick_bm(int M, int Ktot) {
-    const int mode = aero_conv_ring_mode();
+    const AeroRingEnv& env = aero_ring_env();
+    const int mode = env.mode;
     if (!mode || M <= 0 || Ktot % 32) return 0;
-    // shortest contraction the 256-row tile takes (AERO_RING_KMIN256, A/B; 1024 until round 4): the deepest encoder's 1x1 rewrite conv
+    // shortest contraction the 256-row tile takes: 384 (AERO_RING_KMIN256, A/B; 1024 until round 4): the deepest encoder's 1x1 rewrite conv
     // (M 768, K 384: twelve chunks) runs 160 us here WITH its GroupNorm sums against 147 + 35 us (LDS-tiled conv + statistics pass)
-    static int kmin256 = -1;
-    if (kmin256 < 0) { const char* e = getenv("AERO_RING_KMIN256"); kmin256 = e ? atoi(e) : 384; }
-    if (M % 256 == 0 && Ktot >= kmin256) return 256;
-    static int no192 = -1;                                       // AERO_RING_TILE192=0: 128 / 64-row x 512-step tiles instead of the 192 x 256 one (A/B)
-    if (no192 < 0) { const char* e = getenv("AERO_RING_TILE192"); no192 = (e && e[0] == '0') ? 1 : 0; }
+    if (M % 256 == 0 && Ktot >= env.kmin256) return 256;
     // 96-row x 256-step tiles on FOUR waves (two 77-KiB blocks per CU) for contractions with exactly 96 rows (the dilated Conv1d of the
     // deepest DConv: K = 3 x 384): 66 -> 44 us against the 4-wave glds tile.  AERO_RING_HALF=2 also gives the 192 / 384-row decoder convs
     // this tile (round-4 experiment: 694 -> 666 us and 821 -> 831 us -- neutral: those loops are bound by LDS operand bandwidth, ~107 of
     // 128 B/clk per CU for a 96 x 64 wave tile, not by the per-block prologue / epilogue a second resident block would hide); 0 = off
-    static int half = -1;
-    if (half < 0) { const char* e = getenv("AERO_RING_HALF"); half = e ? atoi(e) : 1; }
-    if (mode >= 2 && half && M == 96 && Ktot >= 768) return 96;
-    if (mode >= 2 && half >= 2 && M % 96 == 0 && M <= 384 && Ktot >= 768 && Ktot <= 2048) return 96;
-    if (mode >= 2 && !no192 && M % 192 == 0 && Ktot >= 768) return 192;
+    if (mode >= 2 && env.half && M == 96 && Ktot >= 768) return 96;
+    if (mode >= 2 && env.half >= 2 && M % 96 == 0 && M <= 384 && Ktot >= 768 && Ktot <= 2048) return 96;
+    if (mode >= 2 && env.tile192 && M % 192 == 0 && Ktot >= 768) return 192;
     if (mode >= 2 && M % 128 == 0 && Ktot >= 768) return 128;
     if (mode >= 2 && M % 64 == 0 && Ktot >= 768) return 64;
     return 0;
 }
 
+// the tiles that are instantiated: X(WM, WN, NRB, NT)
+#define AERO_RING_TILES(X) X(2, 2, 4, 3) X(2, 4, 4, 3) X(2, 4, 4, 1) X(1, 4, 3, 3) X(2, 2, 3, 3) X(2, 4, 3, 3) X(1, 8, 4, 3) X(1, 8, 2, 3)
+
 template <int WM, int WN, int NRB, int NT>
-static void aero_conv_ring_go(AeroConvK& p, hipStream_t stream, char* name) {
+static void aero_conv_ring_geom(AeroConvK& p, AeroConvPlan& pl) {
     typedef AeroRingGeom<WM, WN, NRB, NT> G;
-    const aero_conv_desc& d = p.d;
-    p.ntt = (d.T + G::BN - 1) / G::BN;
-    p.nmt = d.M / G::BM;
-    if (name) {
-        snprintf(name, 96, "aero_conv_ring_kernel<%d, %d, %d, %d, 0>", WM, WN, NRB, NT);
-        return;
-    }
-    const long nwg = (long)d.B * d.Fout * p.ntt * p.nmt;
-    const dim3 grid((unsigned)nwg), block(G::NW * 64);
-    const size_t lds = G::SMEM * sizeof(h16);
+    p.ntt = (p.d.T + G::BN - 1) / G::BN;
+    p.nmt = p.d.M / G::BM;
+    pl.grid = (unsigned)((long)p.d.B * p.d.Fout * p.ntt * p.nmt);
+    pl.block = G::NW * 64;
+    pl.lds = G::SMEM * sizeof(h16);
+}
+
+template <int WM, int WN, int NRB, int NT>
+static void aero_conv_ring_go(const AeroConvPlan& pl, const AeroConvK& p, hipStream_t stream) {
+    const dim3 grid(pl.grid), block(pl.block);
 #ifdef AERO_RING_ABLATION
     if constexpr (WM == 2 && NT == 3) {
         static int abl = -1;
         if (abl < 0) { const char* e = getenv("AERO_RING_ABL"); abl = e ? atoi(e) : 0; }
         switch (abl) {
-            case 1: AERO_LAUNCH_DYN((aero_conv_ring_kernel<WM, WN, NRB, NT, 1>), grid, block, lds, stream, p); return;
-            case 2: AERO_LAUNCH_DYN((aero_conv_ring_kernel<WM, WN, NRB, NT, 2>), grid, block, lds, stream, p); return;
-            case 4: AERO_LAUNCH_DYN((aero_conv_ring_kernel<WM, WN, NRB, NT, 4>), grid, block, lds, stream, p); return;
-            case 6: AERO_LAUNCH_DYN((aero_conv_ring_kernel<WM, WN, NRB, NT, 6>), grid, block, lds, stream, p); return;
-            case 8: AERO_LAUNCH_DYN((aero_conv_ring_kernel<WM, WN, NRB, NT, 8>), grid, block, lds, stream, p); return;
-            case 32: AERO_LAUNCH_DYN((aero_conv_ring_kernel<WM, WN, NRB, NT, 32>), grid, block, lds, stream, p); return;
-            case 64: AERO_LAUNCH_DYN((aero_conv_ring_kernel<WM, WN, NRB, NT, 64>), grid, block, lds, stream, p); return;
-            case 128: AERO_LAUNCH_DYN((aero_conv_ring_kernel<WM, WN, NRB, NT, 128>), grid, block, lds, stream, p); return;
+            case 1: AERO_LAUNCH_DYN((aero_conv_ring_kernel<WM, WN, NRB, NT, 1>), grid, block, pl.lds, stream, p); return;
+            case 2: AERO_LAUNCH_DYN((aero_conv_ring_kernel<WM, WN, NRB, NT, 2>), grid, block, pl.lds, stream, p); return;
+            case 4: AERO_LAUNCH_DYN((aero_conv_ring_kernel<WM, WN, NRB, NT, 4>), grid, block, pl.lds, stream, p); return;
+            case 6: AERO_LAUNCH_DYN((aero_conv_ring_kernel<WM, WN, NRB, NT, 6>), grid, block, pl.lds, stream, p); return;
+            case 8: AERO_LAUNCH_DYN((aero_conv_ring_kernel<WM, WN, NRB, NT, 8>), grid, block, pl.lds, stream, p); return;
+            case 32: AERO_LAUNCH_DYN((aero_conv_ring_kernel<WM, WN, NRB, NT, 32>), grid, block, pl.lds, stream, p); return;
+            case 64: AERO_LAUNCH_DYN((aero_conv_ring_kernel<WM, WN, NRB, NT, 64>), grid, block, pl.lds, stream, p); return;
+            case 128: AERO_LAUNCH_DYN((aero_conv_ring_kernel<WM, WN, NRB, NT, 128>), grid, block, pl.lds, stream, p); return;
             default: break;
         }
     }
 #endif
-    AERO_LAUNCH_DYN((aero_conv_ring_kernel<WM, WN, NRB, NT>), grid, block, lds, stream, p);
+    AERO_LAUNCH_DYN((aero_conv_ring_kernel<WM, WN, NRB, NT>), grid, block, pl.lds, stream, p);
 }
 
 #ifndef AERO_RING_ONLY
-AERO_XPART bool aero_conv_ring_try(const aero_conv_desc* d, AeroConvK& p, hipStream_t stream, char* name) {
-    const int mode = aero_conv_ring_mode();
-    if (!mode) return false;
+// eligibility and tile choice; on true, p.ntt / p.nmt / p.tsplit and the plan are this kernel's (p.nT, p.t_step: the regular tap grid)
+AERO_XPART bool aero_conv_ring_plan(const aero_conv_desc* d, AeroConvK& p, AeroConvPlan& pl) {
+    const AeroRingEnv& env = aero_ring_env();
+    if (!env.mode) return false;
     // what the lean epilogue of this kernel covers: bias, activation, fp16 channels-last rows, no trim / residual /
     // embedding / per-item affine / statistics / scatter
     const bool stats_ok = d->stat_mode == 0 || (d->stat_mode == 1 && d->act == AERO_ACT_NONE && d->stats && d->stat_G >= 1 &&
@@ -690,35 +690,38 @@ AERO_XPART bool aero_conv_ring_try(const aero_conv_desc* d, AeroConvK& p, hipStr
         // two full tiles) the narrow tile is neither faster nor slower per launch and 1 % slower in the pipelined step
         // (profiles/r05_ring256_narrow_ab.txt); at T = 376 (config 4: 12->48 kHz, hop 256) the wide tile computes 512 columns for 376:
         // D0 1038 -> 820 us, D1 1118 -> 865 us, config 4's pipelined step 7.07 -> 6.8-6.9 ms (profiles/r05_config4_narrow.txt).
-        // AERO_RING_256X128=0 / 1 forces wide / narrow (A/B).
-        static int narrow256 = -1;
-        if (narrow256 < 0) { const char* e = getenv("AERO_RING_256X128"); narrow256 = e ? atoi(e) : 2; }
-        const bool narrow = narrow256 == 1 || (narrow256 == 2 && (((d->T + 127) / 128) & 1));
-        if (slab3 && narrow) aero_conv_ring_go<2, 2, 4, 3>(p, stream, name);
-        else if (slab3) aero_conv_ring_go<2, 4, 4, 3>(p, stream, name);
-        else aero_conv_ring_go<2, 4, 4, 1>(p, stream, name);
+        const bool narrow = env.narrow256 == 1 || (env.narrow256 == 2 && (((d->T + 127) / 128) & 1));
+        if (slab3 && narrow) pl.tile(AERO_CONV_RING, 2, 2, 4, 3);
+        else if (slab3) pl.tile(AERO_CONV_RING, 2, 4, 4, 3);
+        else pl.tile(AERO_CONV_RING, 2, 4, 4, 1);
     } else if (!slab3) {                                         // (round 4: the 192-row tile with one slab per tap, <2,4,3,1>, was tried for the
         // encoder's strided [8,1] conv with M = 384: 173 us against 168 us on the glds8 tile, and the B = 32 forward no longer matched
         // its two B = 16 halves (2.7e-4) -- the one-phase / one-tap-per-slab combination of the pipeline is unvalidated: not used)
         return false;
     } else if (bm == 96) {
         p.tsplit = 2;                                            // M-tiles adjacent (see the kernel's block order)
-        aero_conv_ring_go<1, 4, 3, 3>(p, stream, name);
-        p.tsplit = 1;
+        pl.tile(AERO_CONV_RING, 1, 4, 3, 3);
     } else if (bm == 192) {
         // Round 5: the 192-row tile on FOUR waves over 128 time steps, two 77-KiB blocks per CU at FULL height -- one
         // block's prologue / epilogue (22 % of a 27-chunk tile's life) runs under the other block's K loop, at twice the weight-tile
         // traffic per FLOP.  Measured against the 8-wave 192 x 256 tile: D2 701 -> 672-699 us, D3 843 -> 807-822 us, bench 8.90 -> 8.81 ms
-        // (profiles/r05_ring_narrow_ab.txt).  AERO_RING_192X128=0 restores the 8-wave tile.
-        static int narrow = -1;
-        if (narrow < 0) { const char* e = getenv("AERO_RING_192X128"); narrow = e ? atoi(e) : 1; }
-        if (narrow) aero_conv_ring_go<2, 2, 3, 3>(p, stream, name);
-        else aero_conv_ring_go<2, 4, 3, 3>(p, stream, name);
+        // (profiles/r05_ring_narrow_ab.txt).
+        if (env.narrow192) pl.tile(AERO_CONV_RING, 2, 2, 3, 3);
+        else pl.tile(AERO_CONV_RING, 2, 4, 3, 3);
     } else if (bm == 128) {
-        aero_conv_ring_go<1, 8, 4, 3>(p, stream, name);
+        pl.tile(AERO_CONV_RING, 1, 8, 4, 3);
     } else {
-        aero_conv_ring_go<1, 8, 2, 3>(p, stream, name);
+        pl.tile(AERO_CONV_RING, 1, 8, 2, 3);
     }
+#define AERO_X(WM, WN, NRB, NT) if (pl.is(WM, WN, NRB, NT)) aero_conv_ring_geom<WM, WN, NRB, NT>(p, pl);
+    AERO_RING_TILES(AERO_X)
+#undef AERO_X
     return true;
+}
+
+AERO_XPART void aero_conv_ring_issue(const AeroConvPlan& pl, const AeroConvK& p, hipStream_t stream) {
+#define AERO_X(WM, WN, NRB, NT) if (pl.is(WM, WN, NRB, NT)) aero_conv_ring_go<WM, WN, NRB, NT>(pl, p, stream);
+    AERO_RING_TILES(AERO_X)
+#undef AERO_X
 }
 #endif
