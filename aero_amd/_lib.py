@@ -256,6 +256,7 @@ _PROTOS = {
     'aero_seanet_conv': (i32, [C.POINTER(SeanetConvDesc), vp]),
     'aero_seanet_resblock': (i32, [C.POINTER(SeanetResDesc), vp]),
     'aero_seanet_conv_out': (i32, [vp, vp, fp, fp, fp, fp, i32, i32, i32, i32, C.c_float, vp]),
+    'aero_segment_gather': (i32, [vp, i32, vp, vp, i32, vp, vp, i32, i32, fp, vp]),
 }
 
 EXPORTS = tuple(_PROTOS)

@@ -1,7 +1,8 @@
 """Minimal WAV I/O (host plumbing) so predict.py / test.py run without torchaudio (absent from the image).
 
 `load(path) -> (float32 tensor [channels, samples] in [-1, 1], sample_rate)` and `save(path, wav, sr)` follow
-torchaudio.load / torchaudio.save as used by the reference (predict.py:53, enhance.py:18-21).
+torchaudio.load / torchaudio.save as used by the reference (predict.py:53, enhance.py:18-21); `load(path, frame_offset, num_frames)` reads
+only that range and `info(path)` only the header (the dataset readers, src/data/audio.py:49-51, data_prep/create_meta_files.py:20-27).
 PCM16 and IEEE float32 RIFF files are supported; torchaudio is used instead when importable.
 """
 import struct
@@ -10,36 +11,77 @@ import numpy as np
 import torch
 
 
-def load(path):
+def _header(f, path):
+    """walk the RIFF chunks of an open file without reading their bodies -> (fmt tuple, data offset, data bytes)"""
+    head = f.read(12)
+    if head[:4] != b'RIFF' or head[8:12] != b'WAVE':
+        raise ValueError(f'{path}: not a RIFF/WAVE file')
+    end = f.seek(0, 2)
+    pos, fmt, data = 12, None, None
+    while pos + 8 <= end:
+        f.seek(pos)
+        cid, size = struct.unpack('<4sI', f.read(8))
+        if cid == b'fmt ':
+            fmt = struct.unpack('<HHIIHH', f.read(16))
+        elif cid == b'data':
+            data = (pos + 8, min(size, end - pos - 8))
+        pos += 8 + size + (size & 1)
+    if fmt is None or data is None:
+        raise ValueError(f'{path}: missing fmt/data chunk')
+    tag, _, _, _, _, bits = fmt
+    if (tag, bits) not in ((1, 16), (3, 32)):
+        raise ValueError(f'{path}: unsupported WAV encoding (tag {tag}, {bits} bit)')
+    return fmt, data[0], data[1]
+
+
+def info(path):
+    """`torchaudio.info` as data_prep/create_meta_files.py uses it -> (n_frames, sample_rate, channels); reads the header only"""
     try:
         import torchaudio
-        return torchaudio.load(str(path))
+        i = torchaudio.info(str(path))
+        return i.num_frames, i.sample_rate, i.num_channels
     except ImportError:
         pass
     with open(path, 'rb') as f:
-        data = f.read()
-    if data[:4] != b'RIFF' or data[8:12] != b'WAVE':
-        raise ValueError(f'{path}: not a RIFF/WAVE file')
-    pos, fmt, pcm = 12, None, None
-    while pos + 8 <= len(data):
-        cid, size = data[pos:pos + 4], struct.unpack('<I', data[pos + 4:pos + 8])[0]
-        body = data[pos + 8:pos + 8 + size]
-        if cid == b'fmt ':
-            fmt = struct.unpack('<HHIIHH', body[:16])
-        elif cid == b'data':
-            pcm = body
-        pos += 8 + size + (size & 1)
-    if fmt is None or pcm is None:
-        raise ValueError(f'{path}: missing fmt/data chunk')
-    tag, nch, sr, _, _, bits = fmt
-    if tag == 1 and bits == 16:
-        a = np.frombuffer(pcm, dtype='<i2').astype(np.float32) / 32768.0
-    elif tag == 3 and bits == 32:
-        a = np.frombuffer(pcm, dtype='<f4').astype(np.float32)
+        (_, nch, sr, _, _, bits), _, nbytes = _header(f, path)
+    return nbytes // (bits // 8) // nch, sr, nch
+
+
+def encoding(path):
+    """'pcm16' or 'f32': how the samples of a supported file are stored"""
+    with open(path, 'rb') as f:
+        fmt, _, _ = _header(f, path)
+    return 'pcm16' if fmt[0] == 1 else 'f32'
+
+
+def load_raw(path, frame_offset=0, num_frames=-1):
+    """the samples as stored: (int16 or float32 array [frames, channels], sample_rate); only the bytes asked for are read"""
+    with open(path, 'rb') as f:
+        (tag, nch, sr, _, _, bits), pos, nbytes = _header(f, path)
+        step = bits // 8 * nch
+        total = nbytes // step
+        first = min(max(int(frame_offset), 0), total)
+        count = total - first if num_frames is None or num_frames < 0 else min(int(num_frames), total - first)
+        f.seek(pos + first * step)
+        raw = f.read(count * step)
+    a = np.frombuffer(raw, dtype='<i2' if tag == 1 else '<f4')
+    return a[:len(a) // nch * nch].reshape(-1, nch), sr
+
+
+def load(path, frame_offset=0, num_frames=-1):
+    """frames [frame_offset, frame_offset + num_frames) of the file (to its end with num_frames = -1; fewer, possibly none, where the file
+    ends first), as torchaudio.load's arguments of the same names (src/data/audio.py:49-51)"""
+    try:
+        import torchaudio
+        return torchaudio.load(str(path), frame_offset=frame_offset, num_frames=num_frames)
+    except ImportError:
+        pass
+    a, sr = load_raw(path, frame_offset, num_frames)
+    if a.dtype == np.int16:
+        a = a.astype(np.float32) / 32768.0
     else:
-        raise ValueError(f'{path}: unsupported WAV encoding (tag {tag}, {bits} bit)')
-    a = a[:len(a) // nch * nch].reshape(-1, nch).T
-    return torch.from_numpy(np.ascontiguousarray(a)), sr
+        a = a.astype(np.float32)
+    return torch.from_numpy(np.ascontiguousarray(a.T)), sr
 
 
 def save(path, wav, sr):

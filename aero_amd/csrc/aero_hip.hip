@@ -49,6 +49,7 @@
 #endif
 #if AERO_IN(9)
 #include "k_seanet.h"
+#include "k_data.h"
 #endif
 
 #include <stdio.h>
@@ -875,6 +876,14 @@ int aero_seanet_conv_out(const void* x, const void* w, const float* bias, const 
                          int32_t C, int32_t Tout, float slope, void* stream) {
     const char* err = "";
     int rc = aero_seanet_conv_out_launch(x, w, bias, skip, stats, y, B, T, C, Tout, slope, (hipStream_t)stream, &err);
+    return aero_finish(rc, err);
+}
+
+// ... and the training data path (k_data.h; aero_amd/data.py): small enough to ride in the same part
+int aero_segment_gather(const void* arena, int32_t is_f32, const int64_t* file_off, const int64_t* file_len, int32_t n_files,
+                        const int32_t* item_file, const int64_t* item_start, int32_t B, int32_t L, float* out, void* stream) {
+    const char* err = "";
+    int rc = aero_segment_gather_launch(arena, is_f32, file_off, file_len, n_files, item_file, item_start, B, L, out, (hipStream_t)stream, &err);
     return aero_finish(rc, err);
 }
 

@@ -5,8 +5,10 @@
     TrainStep         <- src/solver.py:51 (every model through distrib.wrap), :296-320 (forward, losses, optimise),
                          :428-470 (which losses), :475-520 (MelGAN hinge / feature matching), :602-611 (the two optimiser steps)
 
-The Solver around it (epochs, checkpoints, logging, evaluation) is host code outside the path and is not rebuilt; this module is the part
-of it that touches the device.  Everything runs on the HIP kernels: the generator through `AeroFunction`, the criterion through
+    data_source       <- train.py:54-57                    LrHrSet of `dset.train`, device-resident (aero_amd/data.py) or read by the host
+
+Of the Solver around it, the epochs over the training set and the checkpoint package are in train.py; validation, best states, history,
+resuming and logging are host code outside the path and are not rebuilt.  This module is the part that touches the device.  Everything runs on the HIP kernels: the generator through `AeroFunction`, the criterion through
 `losses.MultiResolutionSTFTLoss`, the critic through `Discriminator.generator_losses / discriminator_loss`, both optimisers as
 `FlatAdam`.  With world_size > 1 the gradients of BOTH models are averaged over the ranks inside their backward passes.
 """
@@ -144,3 +146,47 @@ def synthetic_batch(args, batch, device, seed=0):
     lr = torch.randn(batch, 1, n_lr, generator=g)
     hr = 0.1 * torch.randn(batch, 1, n_hr, generator=g)
     return lr.to(device), hr.to(device)
+
+
+class DataSource:
+    """The training set of one rank: `batches(epoch, per_rank)` are the index lists of the epoch in `data.EpochSampler` order (the
+    last may be short), `load(batches)` yields their (lr, hr) on the device -- cut out of the device-resident store (`kind` "device"),
+    or read by the host `LrHrSet` in DataLoader workers ("host").  Both give the same tensors for the same indices."""
+
+    def __init__(self, dataset, store, device, seed, num_workers=0):
+        self.dataset, self.store, self.device, self.seed, self.num_workers = dataset, store, device, seed, num_workers
+        self.kind = 'host' if store is None else 'device'
+
+    def batches(self, epoch, per_rank):
+        from .data import EpochSampler
+        idx = EpochSampler(len(self.dataset), distrib.world_size, distrib.rank, shuffle=True, seed=self.seed, epoch=epoch).indices()
+        return [idx[i:i + per_rank] for i in range(0, len(idx), per_rank)]
+
+    def load(self, batches):
+        if self.store is not None:
+            for b in batches:
+                yield self.store.batch(b)
+            return
+        from torch.utils.data import DataLoader
+        # (not distrib.loader: its sampler would draw an order of its own; the order here is the one `batches` fixed)
+        for lr, hr in DataLoader(self.dataset, batch_sampler=batches, num_workers=self.num_workers):
+            yield lr.to(self.device), hr.to(self.device)
+
+
+def data_source(args, device):
+    """train.py:54-57: the training set of `dset.train` if its lr.json / hr.json exist (and `+synthetic=true` is not given), else None.
+    `+data_on_device=false`, or a set whose decoded samples exceed `+data_max_bytes` (default data.DEFAULT_MAX_BYTES), is read by the host."""
+    import os
+
+    from . import data
+    train = (args.get('dset') or {}).get('train')
+    if args.get('synthetic') or not train:
+        return None
+    if not (os.path.exists(os.path.join(str(train), 'lr.json')) and os.path.exists(os.path.join(str(train), 'hr.json'))):
+        return None
+    exp = args.experiment
+    dataset = data.LrHrSet(train, exp.lr_sr, exp.hr_sr, exp.stride, exp.segment, upsample=exp.upsample)
+    store = None
+    if args.get('data_on_device', True):
+        store = data.DeviceLrHrStore(dataset, device, int(args.get('data_max_bytes', data.DEFAULT_MAX_BYTES)))
+    return DataSource(dataset, store, device, int(args.seed), int(args.get('num_workers', 0)))

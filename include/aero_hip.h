@@ -699,6 +699,16 @@ int aero_seanet_resblock(const aero_seanet_res_desc* d, void* stream);
 int aero_seanet_conv_out(const void* x, const void* w, const float* bias, const float* skip, const float* stats, float* y, int32_t B, int32_t T,
                          int32_t C, int32_t Tout, float slope, void* stream);
 
+/* Training batches out of a device-resident sample arena (csrc/k_data.h; aero_amd/data.py: DeviceLrHrStore; the reference reads every
+ * segment from its file, src/data/audio.py:38-67).  arena: the samples of every file of one side back to back, int16 (PCM16 as stored;
+ * is_f32 = 0) or fp32 (is_f32 = 1); file f holds file_len[f] samples from element file_off[f] (device tables int64 [n_files]).  Item b is the
+ * window [item_start[b], item_start[b] + L) of file item_file[b] (device tables int32 / int64 [B]):
+ *   out fp32 [B][L]:  out[b][t] = 0 <= start + t < len ? arena[off + start + t] (/ 32768 for int16) : 0
+ * Any start, any L, several items of one file; nothing outside [off, off + len) of the item's file is read; an item_file outside
+ * [0, n_files) gives a zero row.  16-byte loads where a vector lies inside the file, 16-byte stores where the output run is aligned. */
+int aero_segment_gather(const void* arena, int32_t is_f32, const int64_t* file_off, const int64_t* file_len, int32_t n_files,
+                        const int32_t* item_file, const int64_t* item_start, int32_t B, int32_t L, float* out, void* stream);
+
 /* RCCL over xGMI behind the same ABI (replaces the NCCL process group of the reference's src/ddp/distrib.py:16-34 for a
  * host that is not PyTorch).  One communicator per process, one process per GPU (hipSetDevice first).  Rank 0 calls aero_comm_unique_id
  * and hands the 128 bytes to the other ranks by any host channel; every rank then calls aero_comm_init with the same bytes.
