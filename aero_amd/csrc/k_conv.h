@@ -245,7 +245,9 @@ static __device__ __forceinline__ void aero_conv_epilogue_generic(const AeroConv
     h16* dst16 = (h16*)d.dst;
     float* dst32 = (float*)d.dst;
     const h16* res = (const h16*)d.res;
-    const bool res_in_copy = p.staged && res != nullptr;       // residual added with coalesced 16-byte loads
+    // residual added with coalesced 16-byte loads in the copy-out -- not under a per-item affine, which applies AFTER the residual
+    // (aero_hip.h, epilogue order): there it is added in registers below, before the scale and shift
+    const bool res_in_copy = p.staged && res != nullptr && !d.batch_scale;
     const float bsc = d.batch_scale ? d.batch_scale[b] : 1.f;
     const float bsh = d.batch_scale ? d.batch_shift[b] : 0.f;
     const int smode = STATS ? d.stat_mode : 0;               // compile-time off: no register/code cost for plain convs

@@ -90,6 +90,7 @@ class Ops:
         self.tag = ''             # engine-set label of the launches being issued ('stack' = Conv2d / ConvTranspose2d of the U-Net)
         self._shape_note = ''
         self._arena, self._cur = {}, None
+        self.on_conv_desc = None  # tests: called with the ConvDesc of every Ops.conv right before its launch (raise = no launch)
 
     @staticmethod
     def stream(t):
@@ -195,10 +196,17 @@ class Ops:
         return pitch.value, toff.value
 
     # -- convolution family --------------------------------------------------------------------
+    def conv_kernel_name(self, d):
+        """the kernel instantiation aero_conv_fwd dispatches the descriptor to (a pure host function of it: no launch, no device)"""
+        buf = C.create_string_buffer(128)
+        self.lib.check(self.lib.cdll.aero_conv_kernel_name(C.byref(d), buf, 128), 'aero_conv_kernel_name')
+        return buf.value.decode()
+
     def conv(self, spec, src0, src1, B, Fin, Fout, T, dst=None, dst_f32=False, dst_f_off=0, dst_F=None, res=None,
              post_add=None, batch_scale=None, batch_shift=None, act=None, dst_strides=None, src0_strides=None,
-             stat=None, scatter=None, tap_split=1, tail=None):
+             stat=None, scatter=None, tap_split=1, tail=None, dry=False):
         """src0/src1: channels-last [B,Fin,T,C] tensors (src0 may be None = zeros).  Returns dst.
+        dry=True: nothing is launched, the call returns the kernel name the plan picks for the descriptor it built (conv_kernel_name).
         tap_split = S > 1 (aero_hip.h "tap split"): S x the blocks, partial sums into an fp32 accumulator, then aero_split_finish.
         tail = fp16 [16][C] image (pack.convtr_tail_image): the fused transposed-conv tail of aero_hip.h -- the activation is not stored,
         the call returns the two fp32 tap-product tensors (lo, hi) [B, Fout, T, 8] for convtr_tail_finish."""
@@ -256,13 +264,15 @@ class Ops:
             d.tap_split, d.split_acc = tap_split, _ptr(split_acc)
         if tail is not None:
             d.tail_w, d.tail_lo, d.tail_hi, d.tail_cp = _ptr(tail), _ptr(tail_lo), _ptr(tail_hi), tail.shape[1]
+        if self.on_conv_desc is not None:
+            self.on_conv_desc(d)
+        if dry:
+            return self.conv_kernel_name(d)
         ref_t = dst if dst is not None else spec.weight
         if self.prof is None:
             self.lib.call('aero_conv_fwd', C.byref(d), self.stream(ref_t))
         else:
-            buf = C.create_string_buffer(128)
-            self.lib.check(self.lib.cdll.aero_conv_kernel_name(C.byref(d), buf, 128), 'aero_conv_kernel_name')
-            kname = buf.value.decode()
+            kname = self.conv_kernel_name(d)
             self._shape_note = (f'conv M={spec.M} C={spec.C0}+{spec.C1}{"(null0)" if src0 is None and spec.C0 else ""} taps={len(spec.df)} '
                                 f'F={Fin}->{Fout} tr={spec.transposed} act={act} res={int(res is not None)} stat={stat["mode"] if stat else 0}')
             pos = B * dst_F * T
