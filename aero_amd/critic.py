@@ -67,6 +67,20 @@ class HipCritic(nn.Module):
         self._pair = None
         self._epoch += 1
 
+    def drop_record(self):
+        """forget the cached D(fake) || D(real) pair (and let go of the signals and activations it keeps alive): after a pass that
+        evaluates the losses without the critic's own step, e.g. validation, so that nothing of it is left for a training step to find"""
+        self._pair = None
+
+    def reset_pack(self):
+        """forget the packed images AND how they are kept up to date (the gather replay compiled at the first weight change): the next
+        forward builds them from the weights by their closures, as the first forward of a process does.  The Solver calls this at
+        every epoch's start, so that an epoch begins from the same engine state whether its process ran the epoch before or loaded it."""
+        self._pair, self._packed, self._key = None, None, None
+        if hasattr(self, '_replay'):
+            self._wflat, self._replay, self._builders = None, None, {}
+        self._epoch += 1
+
     def use_library(self, lib):
         """tests: an explicitly loaded library (the CPU-emulated test double)"""
         self._ops = Ops(lib)

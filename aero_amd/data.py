@@ -276,8 +276,10 @@ def host_batch(lr_hr_set, indices, device):
 
 
 def serialize(models, optimizers, history, best_states, args):
-    """model_serializer.py:19-54 without the best-state files: the package `enhance.load_generator` (and the reference's predict.py /
-    test.py) read, written to `<checkpoint_file>.tmp` and renamed into place"""
+    """model_serializer.py:19-63: the package `enhance.load_generator` (and the reference's predict.py / test.py) read, written to
+    `<checkpoint_file>.tmp` and renamed into place; then, for every entry of `best_states` ({model name: state dict}), that model's
+    package with the best state in it as `<model>_<best_file's name>` next to `best_file`, the same way.  Without best states nothing
+    but the checkpoint is written."""
     package = {
         'models': {name: {'class': m.__class__, 'args': m._init_args_kwargs[0], 'kwargs': m._init_args_kwargs[1],
                           'state': {k: v.detach().cpu().clone() for k, v in m.state_dict().items()}} for name, m in models.items()},
@@ -286,7 +288,16 @@ def serialize(models, optimizers, history, best_states, args):
         'best_states': best_states,
         'args': args,
     }
+    # (beyond the reference's keys) the training engines' host-side state, without which a resumed run is not the interrupted one
+    engines = {name: m.train_state() for name, m in models.items() if hasattr(m, 'train_state')}
+    if any(v is not None for v in engines.values()):
+        package['engines'] = engines
     path = str(args.checkpoint_file)
     torch.save(package, path + '.tmp')
     os.rename(path + '.tmp', path)
+    best_file = str(args.best_file) if best_states else ''
+    for name, state in best_states.items():
+        best = os.path.join(os.path.dirname(best_file), name + '_' + os.path.basename(best_file))
+        torch.save(dict(package['models'][name], state=state), best + '.tmp')
+        os.rename(best + '.tmp', best)
     return package

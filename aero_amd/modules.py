@@ -303,6 +303,26 @@ class Aero(nn.Module):
         if getattr(self, '_train_engine', None) is not None:
             self._train_engine.invalidate()
 
+    def train_state(self):
+        """the training engine's own state for a checkpoint (`TrainEngine.state_dict`); None before the first training forward"""
+        eng = getattr(self, '_train_engine', None)
+        return None if eng is None else eng.state_dict()
+
+    def load_train_state(self, sd):
+        if sd is not None:
+            self._get_train_engine().load_state_dict(sd)
+
+    def reset_train_engine(self):
+        """a new training engine that keeps nothing of the old one but `train_state()`: its weight images are built from the weights by
+        their closures again, and the gather replay is compiled again at the next weight change -- the state the first training forward
+        after a resume starts from.  The Solver calls this at every epoch's start, which makes an epoch the same computation whether its
+        process ran the epoch before or loaded a checkpoint (tests/test_solver.py: a fresh engine and one that has replayed its images
+        for a while give gradients that differ in the last bits)."""
+        sd = self.train_state()
+        if sd is not None:
+            object.__setattr__(self, '_train_engine', None)
+            self.load_train_state(sd)
+
     def __getstate__(self):
         st = self.__dict__.copy()
         st['_engine'] = None

@@ -74,6 +74,17 @@ class TrainEngine:
     def invalidate(self):
         self._epoch += 1
 
+    # ------------------------------------------------------------------ what a resumed run needs besides the weights
+    def state_dict(self):
+        """The host-side state the steps depend on: the forward count and the LayerScale boosts (a power of two per residual branch,
+        read from the weights at the branch's first forward and again every 64 forwards: it positions the fp16 window of the branch's
+        gradients, so a run that resumes must keep the factors and the count the interrupted run had, not read fresh ones)."""
+        return {'nfwd': self._nfwd, 'boosts': {q: [b, at] for q, (b, at) in self._boosts.items()}}
+
+    def load_state_dict(self, sd):
+        self._nfwd = int(sd['nfwd'])
+        self._boosts = {q: (float(b), int(at)) for q, (b, at) in sd['boosts'].items()}
+
     def _sync_weights(self, dev):
         key = (str(dev), self._epoch) + tuple((p.data_ptr(), p._version) for p in self.model.parameters())
         if key == self._key:

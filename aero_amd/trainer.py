@@ -7,8 +7,8 @@
 
     data_source       <- train.py:54-57                    LrHrSet of `dset.train`, device-resident (aero_amd/data.py) or read by the host
 
-Of the Solver around it, the epochs over the training set and the checkpoint package are in train.py; validation, best states, history,
-resuming and logging are host code outside the path and are not rebuilt.  This module is the part that touches the device.  Everything runs on the HIP kernels: the generator through `AeroFunction`, the criterion through
+The Solver around it -- epochs, validation, best states, evaluation, history, checkpoint and resume -- is aero_amd/solver.py.  This module
+is the part that touches the device.  Everything runs on the HIP kernels: the generator through `AeroFunction`, the criterion through
 `losses.MultiResolutionSTFTLoss`, the critic through `Discriminator.generator_losses / discriminator_loss`, both optimisers as
 `FlatAdam`.  With world_size > 1 the gradients of BOTH models are averaged over the ranks inside their backward passes.
 """
@@ -114,7 +114,7 @@ class TrainStep:
             if not exp.get('only_adversarial_loss'):
                 out['generator']['features_' + tag] = feat
             # D(fake.detach()), D(real) on the weights the generator's losses just used (solver.py:478-480): the critic keeps that
-            # record, so this costs no second forward
+            # record, so this costs no second forward (a caller that takes no critic step, as validation does, drops it: drop_record)
             out['discriminator'][name] = critic.discriminator_loss(pr.detach(), hr)
         return out
 
@@ -173,9 +173,10 @@ class DataSource:
             yield lr.to(self.device), hr.to(self.device)
 
 
-def data_source(args, device):
+def data_source(args, device, lib=None):
     """train.py:54-57: the training set of `dset.train` if its lr.json / hr.json exist (and `+synthetic=true` is not given), else None.
-    `+data_on_device=false`, or a set whose decoded samples exceed `+data_max_bytes` (default data.DEFAULT_MAX_BYTES), is read by the host."""
+    `+data_on_device=false`, or a set whose decoded samples exceed `+data_max_bytes` (default data.DEFAULT_MAX_BYTES), is read by the host.
+    lib: tests' explicitly loaded library for the store."""
     import os
 
     from . import data
@@ -188,5 +189,5 @@ def data_source(args, device):
     dataset = data.LrHrSet(train, exp.lr_sr, exp.hr_sr, exp.stride, exp.segment, upsample=exp.upsample)
     store = None
     if args.get('data_on_device', True):
-        store = data.DeviceLrHrStore(dataset, device, int(args.get('data_max_bytes', data.DEFAULT_MAX_BYTES)))
+        store = data.DeviceLrHrStore(dataset, device, int(args.get('data_max_bytes', data.DEFAULT_MAX_BYTES)), lib=lib)
     return DataSource(dataset, store, device, int(args.seed), int(args.get('num_workers', 0)))

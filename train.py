@@ -7,12 +7,17 @@ by the world size (train.py:50-51), Adam for the generator and for the critic (t
 (solver.py:51) and the per-batch step of `Solver._run_one_epoch` (aero_amd/trainer.py).
 
 Two modes.  REAL DATA, when `<dset.train>/lr.json` and `hr.json` exist (train.py:54-57): `LrHrSet` of the experiment's segment / stride,
-`epochs` epochs in `data.EpochSampler` order (seed = args.seed; the last batch of an epoch may be short; `steps=N` caps the total), the
-decoded files resident on the device and every batch cut out of them by aero_segment_gather (`+data_on_device=false`, or a set larger
-than the store's budget: the host reader through a DataLoader, same order, same batches); one JSON line per epoch and, with
-`checkpoint: true`, `checkpoint_file` rewritten by rank 0 after every epoch in the reference's package format (predict.py / test.py load
-it).  SYNTHETIC otherwise, or with `+synthetic=true`: white noise of the experiment's geometry, `steps` batches (default 3), one JSON
-line per step.  Still left out of the Solver: validation during training, best states, the history file, resuming, wandb.
+`epochs` epochs in `data.EpochSampler` order (seed = args.seed; the last batch of an epoch may be short; `steps=N` caps the steps of
+this process), the decoded files resident on the device and every batch cut out of them by aero_segment_gather
+(`+data_on_device=false`, or a set larger than the store's budget: the host reader through a DataLoader, same order, same batches).
+The epoch level is `aero_amd.solver.Solver` (src/solver.py:97-275): with `cross_valid` a validation pass over `dset.valid` every
+`cross_valid_every` epochs and on the last, the best states it finds, every `eval_every` epochs and on the last the LSD over `dset.test`
+with samples in `samples_dir`; one JSON line per epoch, `history_file`, and with `checkpoint: true` `checkpoint_file` (and
+`<model>_<best_file>`) rewritten by rank 0 after every epoch in the reference's package format (predict.py / test.py load it).  A run
+in a directory that holds `checkpoint_file` CONTINUES it -- weights, both Adams, history, best states, the epoch count -- unless
+`restart=true`; `continue_from=<file>` (with `continue_best`, `keep_history`) starts from another run's.  SYNTHETIC otherwise, or with
+`+synthetic=true`: white noise of the experiment's geometry, `steps` batches (default 3), one JSON line per step.  Left out of the
+Solver: wandb, spectrogram PNGs, ViSQOL.
 
 Rendezvous: workers started by `ddp=true` (or by `python -m torch.distributed.run`) find RANK / WORLD_SIZE / MASTER_* in the environment
 (`distrib.init_from_env`: "nccl" = RCCL over xGMI); the reference's own `rank=R world_size=W` + file:// rendezvous is honoured too.
@@ -57,52 +62,6 @@ def run_synthetic(args, step, steps, per_rank, dev):
     return hist
 
 
-def run_epochs(args, step, source, models, optimizers, per_rank, dev):
-    """`epochs` passes over the training set (solver.py:281-320 without validation): -> the per-epoch records, which are also the
-    checkpoint's history"""
-    import torch
-
-    from aero_amd import data, distrib
-    cap = args.get('steps')
-    cap = None if cap is None else int(cap)
-    hist, done = [], 0
-    for epoch in range(int(args.epochs)):
-        if cap is not None and done >= cap:
-            break
-        batches = source.batches(epoch, per_rank)
-        if cap is not None:
-            batches = batches[:cap - done]
-        if dev.type == 'cuda':
-            torch.cuda.synchronize()
-        distrib.barrier()
-        t0 = time.time()
-        acc, keys, seen = None, None, 0
-        for lr, hr in source.load(batches):
-            rec = step(lr, hr)
-            if keys is None:
-                keys = sorted(rec)
-            vals = torch.stack([rec[k].float() for k in keys])
-            acc = vals if acc is None else acc + vals            # (on the device: no host round trip per step)
-            seen += lr.shape[0]
-        if dev.type == 'cuda':
-            torch.cuda.synchronize()
-        dt = distrib.max_over_ranks(time.time() - t0)
-        n = len(batches)
-        done += n
-        avg = distrib.average([v / n for v in acc.tolist()], seen)               # solver.py's logged losses: averaged over ranks
-        vals = dict(zip(keys, avg))
-        if any(v != v or abs(v) == float('inf') for v in vals.values()):
-            raise RuntimeError(f'epoch {epoch}: non-finite loss {vals}')
-        rec = {'epoch': epoch, 'steps': n, 'ms_per_step': round(1e3 * dt / n, 2), 'world_size': distrib.world_size,
-               'batch_per_rank': per_rank, 'data': source.kind, **{k: round(v, 6) for k, v in vals.items()}}
-        hist.append(rec)
-        if distrib.rank == 0:
-            print(json.dumps(rec), flush=True)
-            if args.checkpoint:
-                data.serialize(models, optimizers, hist, {}, args)
-    return hist
-
-
 def run(args):
     import torch
 
@@ -127,8 +86,11 @@ def run(args):
     step = trainer.TrainStep(models, optimizers, args)
     source = trainer.data_source(args, dev)
     if source is not None:
-        hist = run_epochs(args, step, source, models, optimizers, per_rank, dev)
-        steps = sum(h['steps'] for h in hist)
+        from aero_amd.solver import Solver
+        solver = Solver(args, models, optimizers, step, source, dev, per_rank)
+        solver.load()                                            # (after the optimizers exist, before the first step)
+        hist = solver.train()
+        steps = solver.done
     else:
         steps = int(args.get('steps', 3))
         hist = run_synthetic(args, step, steps, per_rank, dev)
