@@ -257,6 +257,8 @@ _PROTOS = {
     'aero_seanet_resblock': (i32, [C.POINTER(SeanetResDesc), vp]),
     'aero_seanet_conv_out': (i32, [vp, vp, fp, fp, fp, fp, i32, i32, i32, i32, C.c_float, vp]),
     'aero_segment_gather': (i32, [vp, i32, vp, vp, i32, vp, vp, i32, i32, fp, vp]),
+    'aero_overlap_stitch': (i32, [fp, i32, fp, i32, fp, i32, i32, i64, i32, i32, i32, fp, i64, vp, vp]),
+    'aero_wav_finalize': (i32, [fp, vp, i32, i64, fp, vp]),
 }
 
 EXPORTS = tuple(_PROTOS)

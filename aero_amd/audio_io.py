@@ -94,11 +94,27 @@ def save(path, wav, sr):
     a = wav.detach().cpu().float().numpy()
     if a.ndim == 1:
         a = a[None]
-    nch, n = a.shape
-    pcm = np.ascontiguousarray(a.T).astype('<f4').tobytes()
+    _write_f32(path, np.ascontiguousarray(a.T), sr)
+
+
+def _write_f32(path, frames, sr):
+    """frames: float32 array [samples, channels], contiguous -- the file's payload as it is stored"""
+    nch = frames.shape[1]
+    pcm = frames.astype('<f4').tobytes()
     hdr = b'RIFF' + struct.pack('<I', 36 + len(pcm)) + b'WAVE' + b'fmt ' + struct.pack('<IHHIIHH', 16, 3, nch, sr, sr * nch * 4, nch * 4, 32)
     with open(path, 'wb') as f:
         f.write(hdr + b'data' + struct.pack('<I', len(pcm)) + pcm)
+
+
+def save_frames(path, frames, sr):
+    """`save` of a payload that is already interleaved: frames float32 [samples, channels] (enhance.write_device) -- the same file as
+    save(path, frames.T, sr)"""
+    try:
+        import torchaudio
+        return torchaudio.save(str(path), frames.cpu().T, sr)
+    except ImportError:
+        pass
+    _write_f32(path, np.ascontiguousarray(frames.detach().cpu().float().numpy()), sr)
 
 
 def resample(waveform, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):

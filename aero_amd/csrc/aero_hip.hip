@@ -50,6 +50,7 @@
 #if AERO_IN(9)
 #include "k_seanet.h"
 #include "k_data.h"
+#include "k_stitch.h"
 #endif
 
 #include <stdio.h>
@@ -884,6 +885,20 @@ int aero_segment_gather(const void* arena, int32_t is_f32, const int64_t* file_o
                         const int32_t* item_file, const int64_t* item_start, int32_t B, int32_t L, float* out, void* stream) {
     const char* err = "";
     int rc = aero_segment_gather_launch(arena, is_f32, file_off, file_len, n_files, item_file, item_start, B, L, out, (hipStream_t)stream, &err);
+    return aero_finish(rc, err);
+}
+
+// ... and the serving path's stitch of overlapped chunks (k_stitch.h; aero_amd/enhance.py)
+int aero_overlap_stitch(const float* y, int32_t Ly, const float* prev, int32_t Lprev, const float* fade, int32_t V, int32_t hop, int64_t k0,
+                        int32_t g, int32_t ch, int32_t last, float* out, int64_t N_out, uint32_t* peak_bits, void* stream) {
+    const char* err = "";
+    int rc = aero_overlap_stitch_launch(y, Ly, prev, Lprev, fade, V, hop, k0, g, ch, last, out, N_out, peak_bits, (hipStream_t)stream, &err);
+    return aero_finish(rc, err);
+}
+
+int aero_wav_finalize(const float* out, const uint32_t* peak_bits, int32_t ch, int64_t N_out, float* wav, void* stream) {
+    const char* err = "";
+    int rc = aero_wav_finalize_launch(out, peak_bits, ch, N_out, wav, (hipStream_t)stream, &err);
     return aero_finish(rc, err);
 }
 

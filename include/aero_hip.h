@@ -709,6 +709,26 @@ int aero_seanet_conv_out(const void* x, const void* w, const float* bias, const 
 int aero_segment_gather(const void* arena, int32_t is_f32, const int64_t* file_off, const int64_t* file_len, int32_t n_files,
                         const int32_t* item_file, const int64_t* item_start, int32_t B, int32_t L, float* out, void* stream);
 
+/* Overlapped chunk outputs of a long file joined on the device (csrc/k_stitch.h; aero_amd/enhance.py: predict_signal(overlap > 0); replaces
+ * the host concatenation of independent chunks, predict.py:85).  Chunk k of the file covers the output samples [k hop, k hop + len(y_k));
+ * neighbouring chunks share V samples.  With k = min(t / hop, n - 1) and j = t - k hop:
+ *   out[c][t] = y_k[c][j]                                   for k = 0 or j >= V
+ *             = p + fade[j] (y_k[c][j] - p),  p = y_{k-1}[c][hop + j]      otherwise        (fade fp32 [V]; written exactly in this form)
+ * One call joins the g equal-length chunk outputs of ONE forward, chunks k0 .. k0 + g - 1 of the file: y fp32 [g ch][Ly], row
+ * k_local ch + c; prev fp32 [ch][Lprev] = the rows of chunk k0 - 1, NULL exactly when k0 = 0.  It writes [k0 hop, (k0 + g) hop) of every
+ * row of out fp32 [ch][N_out], or [k0 hop, (k0 + g - 1) hop + Ly) when `last` is set (the group ends the file), and raises *peak_bits (the
+ * fp32 bits of the running max |out|, zeroed by the caller before the first call) with one atomic max per block.  Gather form: one thread
+ * per four output samples, no atomics on out, the result does not depend on scheduling.  Refused: a null pointer, V > hop, a chunk that
+ * is not the file's last with Ly < hop + V, prev with Lprev < hop + V, a written range outside [0, N_out), a pointer off 4 bytes. */
+int aero_overlap_stitch(const float* y, int32_t Ly, const float* prev, int32_t Lprev, const float* fade, int32_t V, int32_t hop, int64_t k0,
+                        int32_t g, int32_t ch, int32_t last, float* out, int64_t N_out, uint32_t* peak_bits, void* stream);
+
+/* The fp32 payload of the wav file from the stitched signal (csrc/k_stitch.h; aero_amd/enhance.py: write_device; replaces the host
+ * abs().max() and division of enhance.py:18-21): wav fp32 [N_out][ch] interleaved,
+ *   wav[t][c] = out[c][t] / max(peak, 1),  peak = the fp32 whose bits *peak_bits holds
+ * by a correctly rounded fp32 division (not a reciprocal multiply): bit-equal to the host's wav / max(wav.abs().max(), 1). */
+int aero_wav_finalize(const float* out, const uint32_t* peak_bits, int32_t ch, int64_t N_out, float* wav, void* stream);
+
 /* RCCL over xGMI behind the same ABI (replaces the NCCL process group of the reference's src/ddp/distrib.py:16-34 for a
  * host that is not PyTorch).  One communicator per process, one process per GPU (hipSetDevice first).  Rank 0 calls aero_comm_unique_id
  * and hands the 128 bytes to the other ranks by any host channel; every rank then calls aero_comm_init with the same bytes.

@@ -1,9 +1,11 @@
 """predict.py -- enhance one low-resolution wav with the MI355X-native AERO generator.
 
-    python predict.py dset=<dset> experiment=<experiment> +filename=<in.wav> +output=<out dir> [checkpoint_file=...]
+    python predict.py dset=<dset> experiment=<experiment> +filename=<in.wav> +output=<out dir> [checkpoint_file=...] [+overlap_sec=<seconds>]
 
 Same arguments and behaviour as the reference's predict.py:41-99 (10-second independent chunks, concatenation,
 clip-safe normalisation on write); configuration is read from conf/ by aero_amd.config (hydra is optional).
+`+overlap_sec=0.5` (beyond the reference): the chunks overlap by that much and are cross-faded on the device, so the output has no
+step every 10 seconds (aero_amd/enhance.py: predict_signal(overlap=...), write_device).
 """
 import logging
 import os
@@ -29,14 +31,21 @@ def main(argv=None):
         lr_sig = audio_io.resample(lr_sig, sr, args.experiment.hr_sr)
         sr = args.experiment.hr_sr
     logger.info(f'lr wav shape: {tuple(lr_sig.shape)}')
+    overlap = round(float(args.get('overlap_sec') or 0) * sr)       # +overlap_sec=<seconds>: overlapped chunks, cross-faded on the device
     t0 = time.time()
-    pr = enhance.predict_signal(model, lr_sig, sr)
+    if overlap > 0:
+        pr, peak_bits = enhance.predict_signal(model, lr_sig, sr, overlap=overlap, return_device=True)
+    else:
+        pr = enhance.predict_signal(model, lr_sig, sr)
     logger.info(f'prediction duration: {time.time() - t0}')
     logger.info(f'pr wav shape: {tuple(pr.shape)}')
     os.makedirs(args.output, exist_ok=True)
     out = os.path.join(args.output, Path(args.filename).stem + '_pr.wav')
     logger.info(f'saving to: {out}, with sample_rate: {args.experiment.hr_sr}')
-    enhance.write(pr, out, args.experiment.hr_sr)
+    if overlap > 0:
+        enhance.write_device(pr, peak_bits, out, args.experiment.hr_sr)
+    else:
+        enhance.write(pr, out, args.experiment.hr_sr)
     return out
 
 
